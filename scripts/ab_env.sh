@@ -11,7 +11,7 @@ for r in $(seq 1 "$reps"); do
   i=0
   for v in "$@"; do
     i=$((i + 1))
-    env $v timeout -k 10 300 python bench.py --rows "$rows" --steps 8 --warmup 1 > "$O/v${i}_r$r.json" 2> "$O/v${i}_r$r.log" || exit $?
+    env $v timeout -k 10 300 python bench.py --rows "$rows" --steps 8 --warmup 1 --full > "$O/v${i}_r$r.json" 2> "$O/v${i}_r$r.log" || exit $?
     echo "$rows [$v] rep $r: $(grep -o 'step [0-9.]* ms' "$O/v${i}_r$r.log") $(grep -o 'digest=[0-9a-f]*' "$O/v${i}_r$r.log")"
   done
 done

@@ -15,7 +15,7 @@ fi
 for rep in 1 2; do
   for t in "$@"; do
     tag=$(echo "$t" | tr -c 'A-Za-z0-9\n' '_')
-    CDNAML_TUNE="$t" timeout -k 10 300 python bench.py --rows $ROWS --steps 5 --warmup 1 > "$O/ab_$tag.json" 2> "$O/ab_$tag.log" || { tail -5 "$O/ab_$tag.log"; exit 1; }
+    CDNAML_TUNE="$t" timeout -k 10 300 python bench.py --rows $ROWS --steps 5 --warmup 1 --full > "$O/ab_$tag.json" 2> "$O/ab_$tag.log" || { tail -5 "$O/ab_$tag.log"; exit 1; }
     echo "[$t] $(grep 'step ' $O/ab_$tag.log)"
   done
 done

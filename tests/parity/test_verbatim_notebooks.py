@@ -32,9 +32,7 @@ ALLOW = {
 SKIP = {"MLE 04 - Time Series Forecasting.py", "MLE 05 - Databricks Best Practices.py"}
 
 
-def _notebooks():
-    if not os.path.isdir(SOL):
-        return []
+def _on_disk():
     out = []
     for sub in ("", "Labs", "ML Electives"):
         d = os.path.join(SOL, sub)
@@ -44,8 +42,11 @@ def _notebooks():
     return out
 
 
-NOTEBOOKS = _notebooks()
-pytestmark = pytest.mark.skipif(not NOTEBOOKS, reason=f"reference notebooks not found under {SOL}")
+# The notebooks' names are stored (tests/golden/verbatim_notebooks.json: what _on_disk() lists), so the test ids are
+# the same on every machine; the notebooks themselves are only ever read from the reference.
+with open(os.path.join(ROOT, "tests", "golden", "verbatim_notebooks.json")) as _f:
+    NOTEBOOKS = json.load(_f)
+pytestmark = pytest.mark.skipif(not os.path.isdir(SOL), reason=f"reference notebooks not found under {SOL}")
 
 
 def _check(res):
@@ -60,8 +61,7 @@ def _check(res):
 @pytest.fixture(scope="module")
 def cpu_results(tmp_path_factory):
     """Run every notebook on the host in 4 worker processes; {relative notebook path: result}."""
-    if not NOTEBOOKS:
-        return {}
+    assert _on_disk() == NOTEBOOKS, "tests/golden/verbatim_notebooks.json no longer lists the reference's notebooks"
     work = tmp_path_factory.mktemp("verbatim_cpu")
     groups = [NOTEBOOKS[i::4] for i in range(4)]
     env = dict(os.environ, CDNAML_DEVICE="cpu", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""),

@@ -96,7 +96,7 @@ def _bench(tmp_path, nproc, rows="3e4", extra=(), env_extra=None):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     args = [os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--rows", rows, "--steps", "1", "--warmup", "0",
-            *extra]
+            "--full", *extra]  # --full: the bench logs the forest's node count and digest
     if nproc == 1:
         cmd = [sys.executable] + args
     else:
@@ -128,6 +128,25 @@ def test_bench_trains_identical_forest_on_1_2_4_8_ranks(tmp_path):
         if ref is None:
             ref = tag
         assert tag == ref, (w, tag, ref)
+
+
+def test_bench_dump_outputs_repeat_run_for_run(tmp_path):
+    """``--dump-outputs``: the last timed step's forest and predictions as float32 / float64 ``.npy`` files, the same
+    from run to run (the inputs depend on the arguments only); ``--steps`` is the number of timed steps."""
+    import numpy as np
+    dumps = []
+    for i in (0, 1):
+        d = tmp_path / f"dump{i}"
+        res, _ = _bench(tmp_path, 1, rows="5000", extra=("--trees", "2", "--features", "6", "--dump-outputs", str(d)))
+        assert res["ms_per_step"] > 0 and res["value"] == pytest.approx(5000 / (res["ms_per_step"] / 1e3))
+        assert all(f.suffix == ".npy" for f in d.iterdir())
+        dumps.append({f.stem: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"prediction", "prediction_rows", "forest_feat", "forest_thr",
+                                       "forest_value"} <= set(a)
+    assert a["prediction"].shape == (5000,) and len(a["forest_roots"]) == 2
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
 
 
 @pytest.mark.parametrize("scenario,worlds", [("trees", (2, 4)), ("trees_uneven", (2, 4)), ("trees_deep", (2, 3)),

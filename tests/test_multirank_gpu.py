@@ -36,7 +36,7 @@ def _digest(cmd, env):
 @pytest.mark.timeout(600)
 def test_ranks_sharing_one_gpu_grow_the_single_rank_forest():
     env = {**os.environ, "CDNAML_COMM_BACKEND": "gloo", "OMP_NUM_THREADS": "2"}
-    args = ["bench.py", "--rows", "300001", "--steps", "1", "--warmup", "0"]
+    args = ["bench.py", "--rows", "300001", "--steps", "1", "--warmup", "0", "--full"]  # --full: logs the digest
     ref = _digest([sys.executable] + args, env)
     for nproc in (2, 3):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
