@@ -1460,16 +1460,12 @@ def seg_scales(v0p: Optional[torch.Tensor], v1p: torch.Tensor, wmax: int, n_glob
 
 
 SEG_MIN_BLOCKS = 2048
-SEG_ROUND_FIT = True
 # wide-bin (80 < B <= 256, boosting) record levels: work items per level (x ceil(d / 64) feature blocks).  Every block
 # clears and flushes 64 features x B bins of LDS cells into the level histogram with global atomics, so at deep
 # boosting levels (fewer rows, the same number of blocks) the flush -- not the rows -- sets the level time.
 # bench_configs.py gbdt (1e8 x 100, 256 bins), 3 interleaved reps: 1024 -> 28.05-28.23, 768 -> 27.83-27.85,
 # 512 -> 27.78-27.83 ms per tree (profiles/r4/gbdt_min_blocks_ab.txt)
 SEG_MIN_BLOCKS_WIDE = 512
-# three-times-larger record chunks for the six-items-per-wave kernel (its count field is spread over three cell
-# copies): measured 145.1 vs 139.8 ms per headline step (fewer, longer blocks) and neutral at 1.25e7 rows -- off
-LANE10_CHUNK3 = False
 # record histograms through the lane-feature kernel (seg_hist_lane_kernel: lanes own features, bin-major
 # conflict-free LDS planes, one v_perm per cell address); B <= 80 (4 planes <= 80 KB of LDS), 80 < B <= 256:
 # seg_hist_lane4_kernel (64 features per block, a quarter-wave per item; SEG_LANE=False keeps the flat kernel)
@@ -1483,9 +1479,6 @@ REC_PAD = 128
 
 # the record histograms' host planning (_fill_chunk + _seg_work) in the native library (csrc/kernels/plan.hip): ~250 us
 # of numpy per level -> a few us, off the GPU's critical path at the 8-GPU shard size
-NATIVE_PLAN = True
-
-
 def _seg_plan(segs: np.ndarray, chunk: int, B: int, ncu: int, interleave: bool):
     """(chunk, work) = (_fill_chunk(segs, chunk, B, ncu), _seg_work(segs, that chunk, interleave)), natively."""
     segs = np.ascontiguousarray(np.asarray(segs, dtype=np.int64).reshape(-1, 3))
@@ -1630,10 +1623,10 @@ def _seg_items(segs: np.ndarray):
 def _quant(v: torch.Tensor, scale: float, clamp: bool) -> torch.Tensor:
     """The kernels' fixed-point quantisation: rintf(v * scale) in fp32 (clamped to +-2^23 when packed)."""
     q = torch.round(v.float() * torch.tensor(scale, dtype=torch.float32)).to(torch.int64)
-    return q.clamp(-(1 << 23), 1 << 23) if clamp else q
+    return q.clamp(-PACK_Q, PACK_Q) if clamp else q
 
 
-# 3-class packed records (seg.hip kClsSplit): class c's label code is 0 / 1 / CLS3_CODE, so a histogram block's
+# 3-class packed records (packed.h kClsSplit): class c's label code is 0 / 1 / CLS3_CODE, so a histogram block's
 # sum w * q is W1 + 2^22 W2 (W1 < 2^22 inside a block); the kernels' flush splits it into two int64 columns, so the
 # level histograms are [S, d, B, 3] (W, W1, W2) and their global sums have no size bound (round 5 packed
 # W1 + 2^32 W2 in one column: n_global * 255 < 2^32 rows at most)
@@ -1651,14 +1644,40 @@ def cls3_expand(Hb: torch.Tensor) -> torch.Tensor:
     return torch.stack([W - W1 - W2, W1, W2], -1)
 
 
+# the packed item record and LDS cell formats: csrc/kernels/packed.h describes the layouts, these name its numbers
+PACK_SHIFT = 44                  # cell: count << PACK_SHIFT | sum of w * (q + PACK_Q)
+PACK_Q = 1 << 23                 # |q| <= PACK_Q; stored offset by it
+PACK_COUNT_BITS = 64 - PACK_SHIFT
+REC_ROW_BITS = 31                # record: row | w << REC_ROW_BITS | (q + PACK_Q) << (REC_ROW_BITS + REC_W_BITS)
+REC_W_BITS = 8
+_REC_Q_SHIFT = REC_ROW_BITS + REC_W_BITS
+
+
+# cdna_seg_hist mode bits (csrc/kernels/seg.hip SegHistMode)
+SEG_MODE_PACKED = 1        # no v0: count | sum in one packed cell
+SEG_MODE_HAS_W = 2         # per-row weights
+SEG_MODE_ROW_MAJOR = 4     # bins are the row-major copy
+SEG_MODE_FORCE_RM = 8      # seg_hist_rm_kernel even where the flat kernel fits
+SEG_MODE_REC = 16          # perm holds packed item records
+SEG_MODE_LANE = 128        # lane-feature record kernels
+SEG_MODE_ROWS10 = 256      # seg10 rows: the six-items-per-wave kernel
+SEG_MODE_CLS3 = 512        # 3-class records
+
+
+def pack_rows_cap(wm: int) -> int:
+    """Items of weight <= ``wm`` that one packed cell's count field can hold."""
+    return (1 << PACK_COUNT_BITS) // (wm + 1)
+
+
 def rec_decode(rec: torch.Tensor):
     """Packed item records -> (row, weight, quantised label) int64 tensors."""
     r = rec.to(torch.int64)
-    return r & ((1 << 31) - 1), (r >> 31) & 0xFF, ((r >> 39) & ((1 << 25) - 1)) - (1 << 23)
+    return (r & ((1 << REC_ROW_BITS) - 1), (r >> REC_ROW_BITS) & ((1 << REC_W_BITS) - 1),
+            ((r >> _REC_Q_SHIFT) & ((1 << (64 - _REC_Q_SHIFT)) - 1)) - PACK_Q)
 
 
 def rec_encode(rows: torch.Tensor, w: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
-    return rows.to(torch.int64) | (w.to(torch.int64) << 31) | ((q.to(torch.int64) + (1 << 23)) << 39)
+    return rows.to(torch.int64) | (w.to(torch.int64) << REC_ROW_BITS) | ((q.to(torch.int64) + PACK_Q) << _REC_Q_SHIFT)
 
 
 def _seg_hist_rec(bins, d, B, rec, segs, S, wmax, scales, bins_rm, interleave, raw=False, out=None, rm_s10=False,
@@ -1683,22 +1702,18 @@ def _seg_hist_rec(bins, d, B, rec, segs, S, wmax, scales, bins_rm, interleave, r
     else:
         assert bins_rm is not None and rec.dtype == torch.int64
         wm = int(max(1, min(255, wmax)))
-        cap = (1 << 20) // (wm + 1)
-        if rm_s10 and LANE10_CHUNK3:
-            # the six-items-per-wave kernel spreads a block's items over three copies of every cell (item i of the
-            # chunk -> copy i % 3): each copy's 20-bit count holds a third of the chunk
-            cap = 3 * cap - 1024
-        top = SEG_HIST_CHUNK * (3 if rm_s10 and LANE10_CHUNK3 else 1)
+        # one count field per chunk, also for the six-items-per-wave kernel, whose three cell copies could hold
+        # three times the rows: such chunks measured 145.1 vs 139.8 ms per headline step (fewer, longer blocks)
+        cap = pack_rows_cap(wm)
+        top = SEG_HIST_CHUNK
         if rm_s10 and int(segs[:, 1].sum()) > 2 * LANE10_CHUNK_MAX * SEG_MIN_BLOCKS:
             # large levels only: the smaller levels of a shard keep _fill_chunk's round fitting (its chunks grow
             # to drop a sliver round; capping them cost +0.25 ms at 1.25e7 rows)
             top = min(top, LANE10_CHUNK_MAX)
-        ncu = _num_cus(bins.device) if (SEG_ROUND_FIT and rm_s10 and bins.is_cuda) else 0
-        if NATIVE_PLAN:
-            chunk, work = _seg_plan(segs, min(top, cap), B, ncu, interleave)
-        else:
-            chunk = _fill_chunk(segs, min(top, cap), B, ncu)
-            work = _seg_work(segs, chunk, interleave)
+        # seg10 levels fit their chunks to whole rounds of blocks (_fill_chunk, ncu > 0): without it 19.0 / 19.1
+        # vs 18.6 / 18.7 ms per step at 1.25e7 rows (profiles/r4/round_fill_ab.md)
+        ncu = _num_cus(bins.device) if (rm_s10 and bins.is_cuda) else 0
+        chunk, work = _seg_plan(segs, min(top, cap), B, ncu, interleave)
         if len(work) == 0:
             if out is not None:
                 return out
@@ -1707,10 +1722,11 @@ def _seg_hist_rec(bins, d, B, rec, segs, S, wmax, scales, bins_rm, interleave, r
         iout = out if out is not None else torch.zeros((S, d, B, kc), dtype=torch.int64, device=bins.device)
         assert iout.shape == (S, d, B, kc)
         assert bins_rm.shape[0] == n and bins_rm.shape[1] >= G and bins_rm.is_contiguous()
-        mode = 1 | 4 | 16 | (128 if (SEG_LANE and B <= SEG_LANE_MAX_B) else 0) | (512 if cls3 else 0)
+        mode = (SEG_MODE_PACKED | SEG_MODE_ROW_MAJOR | SEG_MODE_REC |
+                (SEG_MODE_LANE if (SEG_LANE and B <= SEG_LANE_MAX_B) else 0) | (SEG_MODE_CLS3 if cls3 else 0))
         if rm_s10:
             assert d <= 100 and B <= 40 and bins_rm.shape[1] == 16
-            mode |= 128 | 256
+            mode |= SEG_MODE_LANE | SEG_MODE_ROWS10
         _lib.check(_lib.lib().cdna_seg_hist(mode, _ptr(bins_rm), n, d, B, _ptr(rec), None, None, None,
                                             _ptr(wt), len(work), 1.0, qs1, _ptr(iout), bins_rm.shape[1],
                                             _stream(bins.device)), "cdna_seg_hist(rec)")
@@ -1721,8 +1737,6 @@ def _seg_hist_rec(bins, d, B, rec, segs, S, wmax, scales, bins_rm, interleave, r
     return out
 
 
-CODES_HIST_BLOCKS = 0
-CODES_ROUND_FILL = True
 _NCU = {}
 
 
@@ -1760,7 +1774,7 @@ def seg_hist_codes(bins_s10: torch.Tensor, d: int, B: int, codes: torch.Tensor, 
     wm = int(max(1, min(255, wmax)))
     sinfo = np.stack([st, sn], 1).astype(np.int32).reshape(-1)
     v1c = v1.float().contiguous()
-    key = (n, d, B, wm, s0, s1, wide, str(codes.device), CODES_HIST_BLOCKS, CODES_ROUND_FILL)
+    key = (n, d, B, wm, s0, s1, wide, str(codes.device))
     work = _ROOT_WORK.get(key)
     if work is None:
         work = _root_work(n, d, wide, wm, s0, s1, codes.device)
@@ -1795,14 +1809,11 @@ _ROOT_WORK: Dict[tuple, np.ndarray] = {}
 def _root_work(n: int, d: int, wide: bool, wm: int, s0: int, s1: int, device) -> np.ndarray:
     """Work items [m, 3] {row start, rows, slot} of a codes histogram over slots [s0, s1) (see seg_hist_codes)."""
     # each LDS cell copy takes every third item of a wave's stream: rows x wmax / 3 (+ a partial trip per
-    # wave) stays below the 20-bit count field (the wide kernel has one copy: rows x wmax)
-    rows = max(64, min(n, (1 << 20) // (wm + 1) - 64 if wide else 3 * ((1 << 20) // (wm + 1)) - 16 * 64))
-    # CODES_HIST_BLOCKS > 0: shrink the row chunks toward that many blocks (>= 16k rows each).  Off by
-    # default: at the per-rank 1.25e7 shape 4096 blocks ran 21.0-21.3 ms per step vs 20.0-20.1 ms with the
-    # largest chunks (the per-block LDS clear + flush of 100 KB outweighs the emptier last round)
+    # wave) stays below the count field (the wide kernel has one copy: rows x wmax).  The largest chunks the field
+    # allows: shrinking them toward 4096 blocks ran 21.0-21.3 vs 20.0-20.1 ms per step at the per-rank 1.25e7
+    # shape (the per-block LDS clear + flush of 100 KB outweighs the emptier last round)
+    rows = max(64, min(n, pack_rows_cap(wm) - 64 if wide else 3 * pack_rows_cap(wm) - 16 * 64))
     S_l = max(1, s1 - s0)
-    if CODES_HIST_BLOCKS > 0:
-        rows = max(min(rows, 16384), min(rows, -(-(n * S_l) // CODES_HIST_BLOCKS)))
     rows = (rows + 63) // 64 * 64
     C = (n + rows - 1) // rows
     bpc = S_l * (-(-d // 64) if wide else 1)  # blocks per row chunk (the wide kernel: one per 64 features)
@@ -1814,7 +1825,7 @@ def _root_work(n: int, d: int, wide: bool, wm: int, s0: int, s1: int, device) ->
             C = C_min
             rows = (-(-n // C) + 63) // 64 * 64
             C = (n + rows - 1) // rows
-    if CODES_ROUND_FILL and C * bpc < 64 * _num_cus(device):
+    if C * bpc < 64 * _num_cus(device):
         # one block per CU: spread the rows over as many chunks as the rounds of blocks already needed can hold,
         # so the last round is full instead of a fraction of the chip (1.25e7 rows x 20 trees: 640 blocks in 2.5
         # rounds -> 760 in 2.97, 19.2 -> 18.9 ms per step; an exact multiple of the CUs, 1280 blocks in 5
@@ -1878,14 +1889,15 @@ def _seg_hist(bins: torch.Tensor, d: int, B: int, perm: torch.Tensor, v0p: Optio
             a0, a1 = w * _quant(v0p[pos], qs0, False), w * _quant(v1p[pos], qs1, False)
         iout = _int_hist_cpu(bins, d, B, S, rows, slot, a0, a1)
     else:
-        chunk = SEG_HIST_CHUNK if not packed else min(SEG_HIST_CHUNK, (1 << 20) // (wm + 1))
+        chunk = SEG_HIST_CHUNK if not packed else min(SEG_HIST_CHUNK, pack_rows_cap(wm))
         chunk = _fill_chunk(segs, chunk, B)
         work = _seg_work(segs, chunk, interleave)
         if len(work) == 0:
             return zero()
         wt, = upload(bins.device, work.reshape(-1))
         iout = torch.zeros((S, d, B, 2), dtype=torch.int64, device=bins.device)
-        mode =(1 if packed else 0) | (2 if wp is not None else 0) | (4 if bins_rm is not None else 0)
+        mode = ((SEG_MODE_PACKED if packed else 0) | (SEG_MODE_HAS_W if wp is not None else 0) |
+                (SEG_MODE_ROW_MAJOR if bins_rm is not None else 0))
         if bins_rm is not None:
             assert bins_rm.shape[0] == n and bins_rm.shape[1] >= G and bins_rm.is_contiguous()
         src = bins if bins_rm is None else bins_rm
@@ -2019,7 +2031,7 @@ def codes_compact(codes: torch.Tensor, tfirst: torch.Tensor, build_slot: np.ndar
     are exact fixed-point sums, so it does not change any result).
 
     rec_scale (GPU, no v0, wave-owned path only): return packed int64 item records instead, as
-    (rec, None, None, None, segs) with rec = row | w << 31 | (clamp(rint(v1 * rec_scale), +-2^23) + 2^23) << 39.
+    (rec, None, None, None, segs) with rec = :func:`rec_encode` of (row, w, clamp(rint(v1 * rec_scale), +-PACK_Q)).
     """
     T, n = codes.shape
     dev = codes.device

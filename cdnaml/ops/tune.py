@@ -4,7 +4,7 @@ The engine's kernel-path switches and sizes are plain module constants (``cdnaml
 ``cdnaml.models.tree.engine``) with the measured defaults documented next to them; tests patch them as module
 attributes.  For an A/B run on a GPU box without editing code::
 
-    CDNAML_TUNE="SEG_MIN_BLOCKS=1024,LANE10_CHUNK3=1" python bench.py
+    CDNAML_TUNE="SEG_MIN_BLOCKS=1024,SEG_LANE=0" python bench.py
 
 sets those constants at import, each value parsed as the type of the default (bool: 0/1/true/false).  A name
 that no tuned module defines is an error, so a typo does not silently measure the default."""

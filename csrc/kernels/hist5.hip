@@ -18,6 +18,7 @@
 // histogram inner loop is hist4f's (rotated features, hoisted VALU work,
 // batched slot-table reads); the next row's record is prefetched.
 #include "common.h"
+#include "packed.h"
 
 namespace {
 
@@ -236,14 +237,33 @@ __global__ __launch_bounds__(kThreads) void hist5_kernel(const Hist5Args a) {
 
 // Packed regression variant (measured motive: the two-atomic kernel reaches
 // ~3.5 of the ~4 LDS atomic lane-ops/clk/CU at full levels): ONE ds_add_u64
-// per update holding count (bits 44..63) | sum of w * (q + 2^23) (bits 0..43).
+// per update into a packed cell (packed.h).
 // Every kPackIters * 512 = 4096 rows the block drains its words into
 // per-thread registers (uint32 count, int64 sum), so count <= 255 * 4096 < 2^20
 // and the offset sum < 4096 * 255 * 2^24 = 2^44: no field can overflow.
-constexpr int kPackShift = 44;
-constexpr int kPackQ = 1 << 23;
 constexpr int kPackIters = 8;
 constexpr int kPackCells = 16;  // plane <= 16 * 512 = 8192 cells (64 KB)
+
+// drain the block's packed LDS cells into the threads' registers (thread t: cells t, t + TH, ...) and zero them
+template <int TH>
+__device__ __forceinline__ void drain_packed(unsigned long long* h64, int plane, uint32_t (&acc_c)[kPackCells],
+                                             long long (&acc_s)[kPackCells]) {
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kPackCells; ++i) {
+    const int idx = (int)threadIdx.x + i * TH;
+    if (idx < plane) {
+      const unsigned long long v = h64[idx];
+      if (v) {
+        const cdna::PackedCell u = cdna::cell_unpack(v);
+        acc_c[i] += (uint32_t)u.cnt;
+        acc_s[i] += u.sum;
+        h64[idx] = 0ull;
+      }
+    }
+  }
+  __syncthreads();
+}
 
 template <bool MASKED, int NT, int TH>
 __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
@@ -339,23 +359,7 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
 #pragma unroll
     for (int k = 0; k < NT; ++k) ocd[k] = (uint32_t)cp[(k < nt ? k : 0) * tstride];
   };
-  auto drain = [&]() {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < kPackCells; ++i) {
-      const int idx = (int)threadIdx.x + i * TH;
-      if (idx < plane) {
-        const unsigned long long v = h64[idx];
-        if (v) {
-          const uint32_t c = (uint32_t)(v >> kPackShift);
-          acc_c[i] += c;
-          acc_s[i] += (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)c;
-          h64[idx] = 0ull;
-        }
-      }
-    }
-    __syncthreads();
-  };
+  auto drain = [&]() { drain_packed<TH>(h64, plane, acc_c, acc_s); };
   int64_t r = rb + threadIdx.x;
   if (r < re) load_row(r, b8, x0, x1, lab, cd);
   else {
@@ -385,9 +389,7 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       cell[j] = foff[j] + (int)__builtin_amdgcn_ubfe(fsel[j] ? hi : lo, (uint32_t)fsh[j], 8u);
-    int q1 = (int)rintf(x1 * a.qs1);
-    q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-    const unsigned long long qoff = (unsigned long long)(q1 + kPackQ);
+    const unsigned long long qoff = cdna::pack_quant(x1, a.qs1);
     const bool row_ok = true;
     const uint32_t cbase_lab = MODE == 1 ? (uint32_t)(lab * plane) : 0u;
     if (row_ok) {
@@ -409,7 +411,7 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
           const uint32_t base = (uint32_t)(ls * slot_cells) + cbase_lab;
           uint32_t mrot = frot;
           if (MASKED) mrot &= ((mk[k] >> rot) | (mk[k] << (8 - rot))) & 0xFFu;
-          const unsigned long long add = ((unsigned long long)wv << kPackShift) + (unsigned long long)wv * qoff;
+          const unsigned long long add = cdna::cell_addend(wv, qoff);
           if (!MASKED && all8) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) atomicAdd(h64 + base + (uint32_t)cell[j], add);
@@ -547,7 +549,7 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
     const uint32_t it_ = (IT);                                                                  \
     const int src_ = (int)(it_ & 127u);                                                         \
     const uint2 bw_ = my_b[src_];                                                               \
-    const unsigned long long qo_ = my_q[src_];                                                  \
+    const uint32_t qo_ = my_q[src_];                                                            \
     const uint32_t wv_ = (it_ >> 7) & 255u;                                                     \
     const int ls_ = (int)(it_ >> 15);                                                           \
     uint32_t mr_ = frot;                                                                        \
@@ -555,7 +557,7 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
       const uint32_t mk_ = lmask[ls_];                                                          \
       mr_ &= ((mk_ >> rot) | (mk_ << (8 - rot))) & 0xFFu;                                       \
     }                                                                                           \
-    const unsigned long long add_ = ((unsigned long long)wv_ << kPackShift) + wv_ * qo_;        \
+    const unsigned long long add_ = cdna::cell_addend(wv_, qo_);                                \
     unsigned long long* hb_ = h64 + ls_ * slot_cells;                                           \
     if (!MASKED && all8) {                                                                      \
       _Pragma("unroll") for (int j = 0; j < 8; ++j)                                             \
@@ -570,23 +572,7 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
     }                                                                                           \
   }
 
-  auto drain = [&]() {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < kPackCells; ++i) {
-      const int idx = (int)threadIdx.x + i * TH;
-      if (idx < plane) {
-        const unsigned long long v = h64[idx];
-        if (v) {
-          const uint32_t c = (uint32_t)(v >> kPackShift);
-          acc_c[i] += c;
-          acc_s[i] += (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)c;
-          h64[idx] = 0ull;
-        }
-      }
-    }
-    __syncthreads();
-  };
+  auto drain = [&]() { drain_packed<TH>(h64, plane, acc_c, acc_s); };
 
   uint64_t b8 = 0;
   float x1 = 0.f;
@@ -626,10 +612,8 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
 #pragma unroll
       for (int k = 0; k < NT; ++k) ncd[k] = 0xFFu;
     }
-    int q1 = (int)rintf(x1 * a.qs1);
-    q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
     my_b[par * 64 + lane] = make_uint2((uint32_t)b8, (uint32_t)(b8 >> 32));
-    my_q[par * 64 + lane] = (uint32_t)(q1 + kPackQ);
+    my_q[par * 64 + lane] = (uint32_t)cdna::pack_quant(x1, a.qs1);
     int lsk[NT];
 #pragma unroll
     for (int k = 0; k < NT; ++k) lsk[k] = lt[k * 256 + (int)(cd[k] & 0xFFu)];

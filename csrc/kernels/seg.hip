@@ -16,14 +16,32 @@
 //     that became leaves are dropped, so perm shrinks level by level.
 // Counts/sums are the same fixed-point integers as hist5 (bit-reproducible).
 #include "common.h"
+#include "packed.h"
 #include <cstdlib>
 
 namespace {
 
+using cdna::cell_addend;
+using cdna::cell_unpack;
+using cdna::kClsSplit;
+using cdna::PackedCell;
+using cdna::rec_addend;
+using cdna::rec_row;
+
 typedef const __attribute__((address_space(4))) uint64_t cu64;  // constant address space: s_load when uniform
 constexpr int kSegThreads = 256;
-constexpr int kPackShift = 44;
-constexpr int kPackQ = 1 << 23;
+
+// cdna_seg_hist mode bits (cdnaml/ops/kernels.py SEG_MODE_*)
+enum SegHistMode : int {
+  kSegPacked = 1,     // no v0: count | sum in one LDS atomic (packed.h cells)
+  kSegHasW = 2,       // per-row weights wp present
+  kSegRowMajor = 4,   // bins are row-major [n][G] words (flat kernel when packed and all groups fit 128 KB of LDS)
+  kSegForceRm = 8,    // force seg_hist_rm_kernel
+  kSegRec = 16,       // `perm` holds packed item records (packed.h)
+  kSegLane = 128,     // with kSegRec | kSegRowMajor, B <= 256: the lane-feature kernels
+  kSegRows10 = 256,   // with kSegLane: bins rows in the seg10 layout (seg_hist_lane10_kernel)
+  kSegCls3 = 512,     // 3-class records (SegHistArgs::cls_split)
+};
 
 // work item: {start in perm, length, slot (hist) / segment (partition)}
 struct SegHistArgs {
@@ -37,38 +55,31 @@ struct SegHistArgs {
   const int* work;
   float qs0, qs1;
   unsigned long long* out;  // [S][d][B][2]
-  // optional packed item records (flat kernel, REC): row | weight << 31 | (q1 + 2^23) << 39 (see CompactWArgs)
-  const uint64_t* rec = nullptr;
+  const uint64_t* rec = nullptr;  // optional packed item records (packed.h)
   int rs = 0;  // row stride of the row-major bins in 8-byte words (0: G); 16 = one 128-byte line per row
-  // 3-class records (kClsSplit): q = 1 (class 1) or 2^22 (class 2), so a block's sum w * q is W1 + 2^22 W2 with
-  // W1 < 3 * 2^20 (the cells' 20-bit counts); the flush re-spaces it to W1 + 2^32 W2 so the global int64 sums of
-  // many blocks (and ranks) keep the two fields apart
-  int cls_split = 0;
+  int cls_split = 0;  // kClsSplit for 3-class records (packed.h), else 0
 };
-
-constexpr int kClsSplit = 22;
 
 // Flush one packed cell's (count, signed sum) into the int64 output: two columns, or for 3-class records
 // (cls_split) three -- (W, W1, W2) with W1 = sum mod 2^22, W2 = sum >> 22 -- so the global sums of many blocks and
 // ranks need no bound on W1 (round 5 re-spaced the sum to W1 + 2^32 W2 in one column, which required
 // n_global * 255 < 2^32, i.e. <= 1.68e7 rows for the packed 3-class path).
-__device__ __forceinline__ void flush_packed(const SegHistArgs& a, int64_t cell, unsigned long long cnt,
-                                             long long sum) {
+__device__ __forceinline__ void flush_packed(const SegHistArgs& a, int64_t cell, const PackedCell u) {
   if (a.cls_split) {
     unsigned long long* o = &a.out[cell * 3];
-    atomicAdd(o, cnt);
-    const long long lo = sum & ((1ll << a.cls_split) - 1ll), hi = sum >> a.cls_split;
+    atomicAdd(o, u.cnt);
+    const long long lo = u.sum & ((1ll << a.cls_split) - 1ll), hi = u.sum >> a.cls_split;
     if (lo) atomicAdd(o + 1, (unsigned long long)lo);
     if (hi) atomicAdd(o + 2, (unsigned long long)hi);
   } else {
     unsigned long long* o = &a.out[cell * 2];
-    atomicAdd(o, cnt);
-    atomicAdd(o + 1, (unsigned long long)sum);
+    atomicAdd(o, u.cnt);
+    atomicAdd(o + 1, (unsigned long long)u.sum);
   }
 }
 
-// PACKED: one u64 atomic per update (count << 44 | sum of w * (q + 2^23)); the
-// host bounds chunk length x max weight below 2^20 so neither field overflows.
+// PACKED: one u64 atomic per update (packed.h cells); the host bounds chunk
+// length x max weight below 2^20 so neither field overflows.
 // !PACKED: two u64 sums (w * q0, w * q1).
 template <bool PACKED, bool HAS_W>
 __global__ __launch_bounds__(kSegThreads) void seg_hist_kernel(const SegHistArgs a) {
@@ -119,10 +130,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_hist_kernel(const SegHistArgs
       for (int j = 0; j < 8; ++j)
         cell[j] = foff[j] + (int)__builtin_amdgcn_ubfe(fsel[j] ? hi : lo, (uint32_t)fsh[j], 8u);
       if (PACKED) {
-        int q1 = (int)rintf(x1[u] * a.qs1);
-        q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-        const unsigned long long add =
-            ((unsigned long long)w[u] << kPackShift) + (unsigned long long)w[u] * (unsigned long long)(q1 + kPackQ);
+        const unsigned long long add = cell_addend(w[u], cdna::pack_quant(x1[u], a.qs1));
         if (all8) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) atomicAdd(h + cell[j], add);
@@ -152,8 +160,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_hist_kernel(const SegHistArgs
     if (PACKED) {
       const unsigned long long v = h[c];
       if (!v) continue;
-      const unsigned long long cnt = v >> kPackShift;
-      flush_packed(a, cell, cnt, (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)cnt);
+      flush_packed(a, cell, cell_unpack(v));
     } else {
       unsigned long long* o = &a.out[cell * 2];
       const unsigned long long v0 = h[c], v1 = h[plane + c];
@@ -226,10 +233,7 @@ __global__ __launch_bounds__(1024) void seg_hist_rm_kernel(const SegHistArgs a, 
       for (int j = 0; j < 8; ++j)
         cell[j] = foff[j] + (int)__builtin_amdgcn_ubfe(fsel[j] ? hi : lo, (uint32_t)fsh[j], 8u);
       if (PACKED) {
-        int q1 = (int)rintf(x1[u] * a.qs1);
-        q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-        const unsigned long long add =
-            ((unsigned long long)w[u] << kPackShift) + (unsigned long long)w[u] * (unsigned long long)(q1 + kPackQ);
+        const unsigned long long add = cell_addend(w[u], cdna::pack_quant(x1[u], a.qs1));
         if (all8) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) atomicAdd(h + cell[j], add);
@@ -260,8 +264,7 @@ __global__ __launch_bounds__(1024) void seg_hist_rm_kernel(const SegHistArgs a, 
     if (PACKED) {
       const unsigned long long v = h[c];
       if (!v) continue;
-      const unsigned long long cnt = v >> kPackShift;
-      flush_packed(a, cell, cnt, (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)cnt);
+      flush_packed(a, cell, cell_unpack(v));
     } else {
       unsigned long long* o = &a.out[cell * 2];
       const unsigned long long v0 = h[c], v1 = h[plane + c];
@@ -310,10 +313,10 @@ __global__ __launch_bounds__(1024) void seg_hist_flat_kernel(const SegHistArgs a
       if (REC) {
         // one 8-byte record per item instead of perm / v1p / wp: fewer, wider loads
         const uint64_t rc = ok ? a.rec[start + i] : 0ull;
-        const int row = (int)(rc & 0x7FFFFFFFull);
+        const int row = (int)rec_row(rc);
         b8[u] = ok ? bins_rm[(int64_t)row * (a.rs ? a.rs : G) + g0 + g] : 0ull;
-        w[u] = (uint32_t)(rc >> 31) & 0xFFu;
-        x1[u] = __int_as_float((int)(uint32_t)(rc >> 39));  // carries q1 + 2^23 (bit pattern, not a float)
+        w[u] = cdna::rec_weight(rc);
+        x1[u] = __int_as_float((int)cdna::rec_qb(rc));  // carries qb (bit pattern, not a float)
       } else {
         const int row = ok ? a.perm[start + i] : 0;
         b8[u] = ok ? bins_rm[(int64_t)row * (a.rs ? a.rs : G) + g0 + g] : 0ull;
@@ -328,16 +331,8 @@ __global__ __launch_bounds__(1024) void seg_hist_flat_kernel(const SegHistArgs a
       const uint32_t fvalid = w[u] == 0u ? 0u : (valid_f >= 8 ? 0xFFu : ((1u << (valid_f > 0 ? valid_f : 0)) - 1u));
       const uint32_t frot = ((fvalid >> rot) | (fvalid << (8 - rot))) & 0xFFu;
       const uint32_t lo = (uint32_t)b8[u], hi = (uint32_t)(b8[u] >> 32);
-      uint32_t qb;  // q1 + 2^23
-      if (REC) {
-        qb = (uint32_t)__float_as_int(x1[u]);
-      } else {
-        int q1 = (int)rintf(x1[u] * a.qs1);
-        q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-        qb = (uint32_t)(q1 + kPackQ);
-      }
-      const unsigned long long add =
-          ((unsigned long long)w[u] << kPackShift) + (unsigned long long)w[u] * (unsigned long long)qb;
+      const uint32_t qb = (uint32_t)(REC ? __float_as_int(x1[u]) : cdna::pack_quant(x1[u], a.qs1));
+      const unsigned long long add = cell_addend(w[u], qb);
       const int gbase = g * plane_g;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -353,11 +348,9 @@ __global__ __launch_bounds__(1024) void seg_hist_flat_kernel(const SegHistArgs a
     const int jj = rem / a.B, bn = rem - jj * a.B;
     const int f = (g0 + gq) * 8 + jj;
     if (f >= a.d) continue;
-    const unsigned long long v = h[c];
-    const unsigned long long cnt = v >> kPackShift;
-    const long long sum = (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)cnt;
-    if (!cnt) continue;
-    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, cnt, sum);
+    const PackedCell u = cell_unpack(h[c]);
+    if (!u.cnt) continue;
+    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, u);
   }
 }
 
@@ -420,12 +413,8 @@ __global__ __launch_bounds__(512) void seg_hist_lane_kernel(const SegHistArgs a,
     unsigned long long add[U];
 #pragma unroll
     for (int p = 0; p < U; ++p) {
-      const uint32_t lo = (uint32_t)rc[p], hi = (uint32_t)(rc[p] >> 32);
-      const uint32_t row = lo & 0x7FFFFFFFu;
-      x[p] = *reinterpret_cast<const uint32_t*>(lbase + (uint64_t)row * (uint64_t)row_bytes);
-      const uint32_t w = __builtin_amdgcn_alignbit(hi, lo, 31) & 0xFFu;
-      const uint32_t qb = hi >> 7;  // q1 + 2^23
-      add[p] = ((unsigned long long)(w << (kPackShift - 32)) << 32) + (unsigned long long)w * qb;
+      x[p] = *reinterpret_cast<const uint32_t*>(lbase + (uint64_t)rec_row(rc[p]) * (uint64_t)row_bytes);
+      add[p] = rec_addend(rc[p]);
     }
 #pragma unroll
     for (int p = 0; p < U; ++p) {
@@ -444,9 +433,7 @@ __global__ __launch_bounds__(512) void seg_hist_lane_kernel(const SegHistArgs a,
     if (bn >= a.B || f >= a.d) continue;
     const unsigned long long v = h[c];
     if (!v) continue;
-    const unsigned long long cnt = v >> kPackShift;
-    const long long sum = (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)cnt;
-    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, cnt, sum);
+    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, cell_unpack(v));
   }
 }
 
@@ -496,16 +483,13 @@ __global__ __launch_bounds__(1024, 2) void seg_hist_lane8_kernel(const SegHistAr
     uint2 x[U];
 #pragma unroll
     for (int p = 0; p < U; ++p) {
-      uint32_t row = (uint32_t)rc[p] & 0x7FFFFFFFu;
+      uint32_t row = rec_row(rc[p]);
       if (!CDNA_DCHECK((int64_t)row < a.n, 0x5E81u)) row = 0u;  // record row outside the bins
       x[p] = *reinterpret_cast<const uint2*>(lbase + (uint64_t)row * (uint64_t)row_bytes);
     }
 #pragma unroll
     for (int p = 0; p < U; ++p) {
-      const uint32_t lo = (uint32_t)rc[p], hi = (uint32_t)(rc[p] >> 32);
-      const uint32_t w = __builtin_amdgcn_alignbit(hi, lo, 31) & 0xFFu;
-      const unsigned long long add = ((unsigned long long)(w << (kPackShift - 32)) << 32) +
-                                     (unsigned long long)w * (hi >> 7);
+      const unsigned long long add = rec_addend(rc[p]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const uint32_t off = __builtin_amdgcn_perm(loff, j < 4 ? x[p].x : x[p].y, 0x0C0C0004u | ((uint32_t)(j & 3) << 8));
@@ -521,12 +505,9 @@ __global__ __launch_bounds__(1024, 2) void seg_hist_lane8_kernel(const SegHistAr
     const int f = f0 + 8 * l + j;
     if (bn >= a.B || f >= a.d) continue;
     const unsigned long long* cell = h + j * PLANE + bn * 32 + l;
-    const unsigned long long v0 = cell[0], v1 = cell[16];
-    const unsigned long long cnt = (v0 >> kPackShift) + (v1 >> kPackShift);
-    if (!cnt) continue;
-    const unsigned long long m = (1ull << kPackShift) - 1ull;
-    const long long sum = (long long)((v0 & m) + (v1 & m)) - (long long)kPackQ * (long long)cnt;
-    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, cnt, sum);
+    const PackedCell u = cell_unpack(cell[0], cell[16]);
+    if (!u.cnt) continue;
+    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, u);
   }
 }
 
@@ -546,25 +527,85 @@ __global__ __launch_bounds__(1024, 2) void seg_hist_lane8_kernel(const SegHistAr
 // bins (cell byte address bin << 8 | l' << 3: one v_perm_b32, as in lane8);
 // the flush adds the three copies.  LDS = BP * 2.5 KB (100 KB at 40 bins:
 // one 1024-thread block per CU).
+template <int CELLS>  // zero a 1024-thread block's LDS cells
+__device__ __forceinline__ void clear_cells(unsigned long long* h) {
+  for (int i = threadIdx.x; i < CELLS; i += 1024) h[i] = 0ull;
+  __syncthreads();
+}
+
+// The tile: a lane's place in it, one trip of U records per lane, and the flush.  seg_hist_lane10_kernel feeds it
+// from the record buffer, seg_hist_lane10_root_kernel from its codes ring.
+template <int BP>
+struct Lane10Tile {
+  static constexpr int TH = 1024, NW = TH / 64, IPW = 6;
+  static constexpr int PLANE = BP * 32;  // u64 cells per feature plane j
+  static constexpr int CELLS = 10 * PLANE;  // [10][BP][32]
+  bool on;  // c < 3 (lanes 30 / 31 of each half: no item)
+  int item;  // the lane's item of the wave's six
+  const uint8_t* lbase;
+  uint32_t loff;  // column << 3
+
+  __device__ __forceinline__ explicit Lane10Tile(const uint8_t* bins8) {
+    const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
+    const int c = l32 / 10, s = l32 - 10 * c;
+    on = c < 3;
+    item = half * 3 + (on ? c : 0);
+    lbase = bins8 + 12 * (on ? s : 0);
+    loff = (uint32_t)l32 * 8u;
+  }
+
+  // U records per lane (record 0 where the lane has none): U dwordx3 gathers, then 10 atomics per record
+  template <int U>
+  __device__ __forceinline__ void trip(unsigned long long* h, const SegHistArgs& a, const uint64_t (&rc)[U]) const {
+    uint32_t x0[U], x1[U], x2[U];
+#pragma unroll
+    for (int p = 0; p < U; ++p) {
+      uint32_t row = rec_row(rc[p]);
+      if (!CDNA_DCHECK((int64_t)row < a.n, 0x5E84u)) row = 0u;  // record row outside the bins
+      const uint3 v = *reinterpret_cast<const uint3*>(lbase + (uint64_t)row * 128u);
+      x0[p] = v.x; x1[p] = v.y; x2[p] = v.z;
+    }
+#pragma unroll
+    for (int p = 0; p < U; ++p) {
+      const unsigned long long add = rec_addend(rc[p]);
+#pragma unroll
+      for (int j = 0; j < 10; ++j) {
+        const uint32_t src = j < 4 ? x0[p] : (j < 8 ? x1[p] : x2[p]);
+        const uint32_t off = __builtin_amdgcn_perm(loff, src, 0x0C0C0004u | ((uint32_t)(j & 3) << 8));
+        atomicAdd(reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h) + off) + j * PLANE, add);
+      }
+    }
+  }
+
+  // thread -> (plane j, bin, chunk s), the three item copies summed into output slot `oslot`
+  static __device__ __forceinline__ void flush(const unsigned long long* h, const SegHistArgs& a, int oslot) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < 10 * BP * 10; e += TH) {
+      const int sc = e % 10, rest = e / 10;
+      const int bn = rest % BP, j = rest / BP;
+      const int f = 10 * sc + j;
+      if (bn >= a.B || f >= a.d) continue;
+      const unsigned long long* cell = h + j * PLANE + bn * 32 + sc;
+      const PackedCell u = cell_unpack(cell[0], cell[10], cell[20]);
+      if (!u.cnt) continue;
+      flush_packed(a, ((int64_t)oslot * a.d + f) * a.B + bn, u);
+    }
+  }
+};
+
 template <int BP, int U>
 __global__ __launch_bounds__(1024) void seg_hist_lane10_kernel(const SegHistArgs a, const uint8_t* __restrict__ bins8) {
-  constexpr int TH = 1024, NW = TH / 64, IPW = 6;
-  constexpr int PLANE = BP * 32;  // u64 cells per feature plane j
-  __shared__ __attribute__((aligned(16))) unsigned long long h[10 * PLANE];  // [10][BP][32]
+  using Tile = Lane10Tile<BP>;
+  constexpr int NW = Tile::NW, IPW = Tile::IPW;
+  __shared__ __attribute__((aligned(16))) unsigned long long h[Tile::CELLS];
   const int start = a.work[3 * blockIdx.x], slot = a.work[3 * blockIdx.x + 2];
   const int len = a.work[3 * blockIdx.x + 1];
   if (!CDNA_DCHECK(start >= 0 && len >= 0 && slot >= 0, 0x5E83u)) return;  // corrupt work item
-  for (int i = threadIdx.x; i < 10 * PLANE; i += TH) h[i] = 0ull;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
-  const int c = l32 / 10, s = l32 - 10 * c;  // c = 3: lanes 30 / 31 (no item)
-  const bool on = c < 3;
-  const int item = half * 3 + (on ? c : 0);
+  clear_cells<Tile::CELLS>(h);
+  const Tile t(bins8);
   const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint8_t* lbase = bins8 + 12 * (on ? s : 0);
-  const uint32_t loff = (uint32_t)l32 * 8u;  // column << 3
   static_assert(IPW * U <= 128, "record over-read must stay within REC_PAD");
-  const uint64_t* __restrict__ recp = a.rec + start + item;
+  const uint64_t* __restrict__ recp = a.rec + start + t.item;
   // U = 16 items per lane per trip (160 atomics): the trip's record load and gather latencies are exposed
   // once per trip, so the other 15 waves of the CU need ~15 x 160 ds_add_u64 of work to cover them (U = 8:
   // 13.7 ms per level; a two-set software pipeline did not survive the compiler's loop rotation; round 6: the
@@ -574,51 +615,17 @@ __global__ __launch_bounds__(1024) void seg_hist_lane10_kernel(const SegHistArgs
     uint64_t rc[U];
 #pragma unroll
     for (int p = 0; p < U; ++p) rc[p] = recp[i0 + IPW * p];
-    if (!on) {
+    if (!t.on) {
 #pragma unroll
       for (int p = 0; p < U; ++p) rc[p] = 0ull;
     } else if (i0 + IPW * U > len) {
 #pragma unroll
       for (int p = 0; p < U; ++p)
-        if (i0 + IPW * p + item >= len) rc[p] = 0ull;
+        if (i0 + IPW * p + t.item >= len) rc[p] = 0ull;
     }
-    uint32_t x0[U], x1[U], x2[U];
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      uint32_t row = (uint32_t)rc[p] & 0x7FFFFFFFu;
-      if (!CDNA_DCHECK((int64_t)row < a.n, 0x5E84u)) row = 0u;  // record row outside the bins
-      const uint3 v = *reinterpret_cast<const uint3*>(lbase + (uint64_t)row * 128u);
-      x0[p] = v.x; x1[p] = v.y; x2[p] = v.z;
-    }
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t lo = (uint32_t)rc[p], hi = (uint32_t)(rc[p] >> 32);
-      const uint32_t w = __builtin_amdgcn_alignbit(hi, lo, 31) & 0xFFu;
-      const unsigned long long add = ((unsigned long long)(w << (kPackShift - 32)) << 32) +
-                                     (unsigned long long)w * (hi >> 7);
-#pragma unroll
-      for (int j = 0; j < 10; ++j) {
-        const uint32_t src = j < 4 ? x0[p] : (j < 8 ? x1[p] : x2[p]);
-        const uint32_t off = __builtin_amdgcn_perm(loff, src, 0x0C0C0004u | ((uint32_t)(j & 3) << 8));
-        atomicAdd(reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h) + off) + j * PLANE, add);
-      }
-    }
+    t.trip(h, a, rc);
   }
-  __syncthreads();
-  // flush: thread -> (plane j, bin, chunk s), the three item copies summed
-  for (int e = threadIdx.x; e < 10 * BP * 10; e += TH) {
-    const int sc = e % 10, rest = e / 10;
-    const int bn = rest % BP, j = rest / BP;
-    const int f = 10 * sc + j;
-    if (bn >= a.B || f >= a.d) continue;
-    const unsigned long long* cell = h + j * PLANE + bn * 32 + sc;
-    const unsigned long long v0 = cell[0], v1 = cell[10], v2 = cell[20];
-    const unsigned long long cnt = (v0 >> kPackShift) + (v1 >> kPackShift) + (v2 >> kPackShift);
-    if (!cnt) continue;
-    const unsigned long long m = (1ull << kPackShift) - 1ull;
-    const long long sum = (long long)((v0 & m) + (v1 & m) + (v2 & m)) - (long long)kPackQ * (long long)cnt;
-    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, cnt, sum);
-  }
+  Tile::flush(h, a, slot);
 }
 
 // Levels with at most one built node per tree (level 0: the roots; level 1:
@@ -645,117 +652,106 @@ struct RootDraw {
   cdna::PoissonCdf cdf;
 };
 
+// One wave's ring of records compacted from the row codes (both root kernels).  RING entries of LDS; a trip
+// consumes up to NI of them, lane by lane: NI - 1 + 64 < RING, so a refill window never overwrites unread entries.
+template <int RING, int NI, bool DRAW>
+struct CodesRing {
+  static_assert((RING & (RING - 1)) == 0 && NI - 1 + 64 < RING, "ring size");
+  uint64_t* rg;
+  const uint16_t* ct;  // the tree's codes
+  const float* v1;
+  float qs1;
+  int tree;
+  uint32_t node;
+  const RootDraw* dr;  // DRAW only
+  int lane;
+  int64_t wr, wend;  // the wave's rows: a contiguous 64-aligned share of the block's range [r0, r0 + len)
+  uint32_t head = 0u, tail = 0u;  // wave-uniform ring cursors
+  uint32_t ncw = 0xFFu;  // the window in flight: the lane's row code and label
+  float ny = 0.f;
+
+  __device__ __forceinline__ CodesRing(uint64_t* ring_lds, const uint16_t* codes, int64_t n, const float* v1_,
+                                       float qs1_, int tree_, uint32_t node_, int r0, int len, int wid, int nw,
+                                       const RootDraw* dr_)
+      : rg(ring_lds), ct(codes + (int64_t)tree_ * n), v1(v1_), qs1(qs1_), tree(tree_), node(node_), dr(dr_),
+        lane(threadIdx.x & 63) {
+    const int per = ((len + nw - 1) / nw + 63) & ~63;
+    wr = (int64_t)r0 + (int64_t)wid * per;
+    wend = (int64_t)r0 + len < wr + per ? (int64_t)r0 + len : wr + per;
+    fetch(wr + lane);
+  }
+
+  __device__ __forceinline__ void fetch(int64_t r) {
+    if (DRAW) {
+      const uint32_t w = cdna::poisson_draw(cdna::bootstrap_uniform(dr->seed, dr->offset + (uint64_t)r, tree),
+                                            dr->cdf, dr->rate);
+      ncw = (w << 8) | (w ? 0u : 0xFFu);
+      if (r < wend) const_cast<uint16_t*>(ct)[r] = (uint16_t)ncw;
+      else ncw = 0xFFu;
+    } else {
+      ncw = r < wend ? (uint32_t)ct[r] : 0xFFu;
+    }
+    ny = r < wend ? v1[r] : 0.f;
+  }
+
+  // Until the rows are exhausted and the ring drained: refill to NI entries, hand `body` the lane's U records of
+  // the trip -- entries first + stride * p of the queued ones (stride * U = NI), record 0 past them or when !on.
+  template <int U, typename F>
+  __device__ __forceinline__ void for_each_trip(int first, int stride, bool on, F&& body) {
+    for (;;) {
+      while (tail - head < (uint32_t)NI && wr < wend) {  // wave-uniform refill, one 64-row window per round
+        const uint32_t cw = ncw;
+        const float y = ny;
+        const int64_t r = wr + lane;
+        wr += 64;
+        fetch(wr + lane);
+        const bool has = (cw & 0xFFu) == node && (cw >> 8) != 0u;
+        const uint64_t m = __builtin_amdgcn_ballot_w64(has);
+        if (has) {
+          const uint32_t rank =
+              __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+          rg[(tail + rank) & (RING - 1)] = cdna::rec_encode((uint64_t)r, cw >> 8, y, qs1);
+        }
+        tail += (uint32_t)__builtin_popcountll(m);
+      }
+      const uint32_t avail = tail - head;
+      if (avail == 0u) break;  // wave-uniform
+      asm volatile("" ::: "memory");  // the ring writes above are issued before the reads below (LDS: in order)
+      uint64_t rc[U];
+#pragma unroll
+      for (int p = 0; p < U; ++p) {
+        const uint32_t k = (uint32_t)(stride * p + first);
+        rc[p] = (on && k < avail) ? rg[(head + k) & (RING - 1)] : 0ull;
+      }
+      head += avail < (uint32_t)NI ? avail : (uint32_t)NI;
+      body(rc);
+      asm volatile("" ::: "memory");  // this trip's ring reads are issued before the next refill overwrites
+    }
+  }
+};
+
 template <int BP, bool DRAW>
 __global__ __launch_bounds__(1024) void seg_hist_lane10_root_kernel(const SegHistArgs a, const uint8_t* __restrict__ bins8,
                                                                     const uint16_t* __restrict__ codes,
                                                                     const float* __restrict__ v1, float qs1,
                                                                     const int* __restrict__ sinfo, int slot0,
                                                                     const RootDraw dr) {
-  constexpr int TH = 1024, NW = TH / 64, U = 16, IPW = 6, NI = IPW * U, RING = 256;  // NI - 1 + 64 < RING
-  constexpr int PLANE = BP * 32;
-  __shared__ __attribute__((aligned(16))) unsigned long long h[10 * PLANE];  // [10][BP][32]
+  using Tile = Lane10Tile<BP>;
+  constexpr int NW = Tile::NW, U = 16, IPW = Tile::IPW, NI = IPW * U, RING = 256;
+  __shared__ __attribute__((aligned(16))) unsigned long long h[Tile::CELLS];
   __shared__ __attribute__((aligned(16))) uint64_t ring[NW][RING];
   const int r0 = a.work[3 * blockIdx.x], len = a.work[3 * blockIdx.x + 1], slot = a.work[3 * blockIdx.x + 2];
   const int tree = sinfo[2 * slot];
   const uint32_t node = (uint32_t)sinfo[2 * slot + 1];
   if (!CDNA_DCHECK(r0 >= 0 && len >= 0 && slot >= slot0 && tree >= 0 && node < 0xFFu && (int64_t)r0 + len <= a.n,
                    0x5E85u)) return;
-  for (int i = threadIdx.x; i < 10 * PLANE; i += TH) h[i] = 0ull;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
-  const int c = l32 / 10, s = l32 - 10 * c;
-  const bool on = c < 3;
-  const int item = half * 3 + (on ? c : 0);
+  clear_cells<Tile::CELLS>(h);
+  const Tile t(bins8);
   const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint8_t* lbase = bins8 + 12 * (on ? s : 0);
-  const uint32_t loff = (uint32_t)l32 * 8u;
-  const uint16_t* ct = codes + (int64_t)tree * a.n;
-  uint16_t* cw_out = DRAW ? const_cast<uint16_t*>(ct) : nullptr;
-  uint64_t* rg = ring[wid];
-  // the wave's rows: a contiguous 64-aligned share of the block's range
-  const int per = ((len + NW - 1) / NW + 63) & ~63;
-  int64_t wr = (int64_t)r0 + (int64_t)wid * per;
-  const int64_t wend = (int64_t)r0 + len < wr + per ? (int64_t)r0 + len : wr + per;
-  uint32_t head = 0u, tail = 0u;  // wave-uniform ring cursors
-  uint32_t ncw = 0xFFu;
-  float ny = 0.f;
-  auto fetch = [&](int64_t r) {
-    if (DRAW) {
-      const uint32_t w = cdna::poisson_draw(cdna::bootstrap_uniform(dr.seed, dr.offset + (uint64_t)r, tree), dr.cdf,
-                                            dr.rate);
-      ncw = (w << 8) | (w ? 0u : 0xFFu);
-      if (r < wend) cw_out[r] = (uint16_t)ncw;
-      else ncw = 0xFFu;
-    } else {
-      ncw = r < wend ? (uint32_t)ct[r] : 0xFFu;
-    }
-    ny = r < wend ? v1[r] : 0.f;
-  };
-  fetch(wr + lane);
-  for (;;) {
-    while (tail - head < (uint32_t)NI && wr < wend) {  // wave-uniform refill, one 64-row window per round
-      const uint32_t cw = ncw;
-      const float y = ny;
-      const int64_t r = wr + lane;
-      wr += 64;
-      fetch(wr + lane);
-      const bool has = (cw & 0xFFu) == node && (cw >> 8) != 0u;
-      const uint64_t m = __builtin_amdgcn_ballot_w64(has);
-      if (has) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        int q1 = (int)rintf(y * qs1);
-        q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-        rg[(tail + rank) & (RING - 1)] =
-            (uint64_t)r | ((uint64_t)(cw >> 8) << 31) | ((uint64_t)(uint32_t)(q1 + kPackQ) << 39);
-      }
-      tail += (uint32_t)__builtin_popcountll(m);
-    }
-    const uint32_t avail = tail - head;
-    if (avail == 0u) break;  // wave-uniform: rows exhausted and ring drained
-    asm volatile("" ::: "memory");  // the ring writes above are issued before the reads below (LDS: in order)
-    uint64_t rc[U];
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t k = (uint32_t)(IPW * p + item);
-      rc[p] = (on && k < avail) ? rg[(head + k) & (RING - 1)] : 0ull;
-    }
-    head += avail < (uint32_t)NI ? avail : (uint32_t)NI;
-    uint32_t x0[U], x1[U], x2[U];
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t row = (uint32_t)rc[p] & 0x7FFFFFFFu;
-      const uint3 v = *reinterpret_cast<const uint3*>(lbase + (uint64_t)row * 128u);
-      x0[p] = v.x; x1[p] = v.y; x2[p] = v.z;
-    }
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t lo = (uint32_t)rc[p], hi = (uint32_t)(rc[p] >> 32);
-      const uint32_t w = __builtin_amdgcn_alignbit(hi, lo, 31) & 0xFFu;
-      const unsigned long long add = ((unsigned long long)(w << (kPackShift - 32)) << 32) +
-                                     (unsigned long long)w * (hi >> 7);
-#pragma unroll
-      for (int j = 0; j < 10; ++j) {
-        const uint32_t src = j < 4 ? x0[p] : (j < 8 ? x1[p] : x2[p]);
-        const uint32_t off = __builtin_amdgcn_perm(loff, src, 0x0C0C0004u | ((uint32_t)(j & 3) << 8));
-        atomicAdd(reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h) + off) + j * PLANE, add);
-      }
-    }
-    asm volatile("" ::: "memory");  // this trip's ring reads are issued before the next refill overwrites
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 10 * BP * 10; e += TH) {
-    const int sc = e % 10, rest = e / 10;
-    const int bn = rest % BP, j = rest / BP;
-    const int f = 10 * sc + j;
-    if (bn >= a.B || f >= a.d) continue;
-    const unsigned long long* cell = h + j * PLANE + bn * 32 + sc;
-    const unsigned long long v0 = cell[0], v1c = cell[10], v2 = cell[20];
-    const unsigned long long cnt = (v0 >> kPackShift) + (v1c >> kPackShift) + (v2 >> kPackShift);
-    if (!cnt) continue;
-    const unsigned long long m = (1ull << kPackShift) - 1ull;
-    const long long sum = (long long)((v0 & m) + (v1c & m) + (v2 & m)) - (long long)kPackQ * (long long)cnt;
-    flush_packed(a, ((int64_t)(slot - slot0) * a.d + f) * a.B + bn, cnt, sum);
-  }
+  CodesRing<RING, NI, DRAW> rq(ring[wid], codes, a.n, v1, qs1, tree, node, r0, len, wid, NW, &dr);
+  rq.template for_each_trip<U>(t.item, IPW, t.on,
+                               [&](const uint64_t(&rc)[U]) __attribute__((always_inline)) { t.trip(h, a, rc); });
+  Tile::flush(h, a, slot - slot0);
 }
 
 // Wide-bin lane variant (80 < B <= 256: XGBoost-style 256-bin boosting).  Four
@@ -776,53 +772,39 @@ __global__ __launch_bounds__(1024) void seg_hist_lane10_root_kernel(const SegHis
 // back, so the second half of each gathered 128-byte row line hits the L2 the
 // first half filled (the x-major 2-D order re-fetched every line: 867 -> 789 ms
 // per 20 trees when fixed).
-template <int BP, int U>
-__global__ __launch_bounds__(1024) void seg_hist_lane4_kernel(const SegHistArgs a, const uint8_t* __restrict__ bins8,
-                                                              int row_bytes, int nwork, int ny) {
-  constexpr int TH = 1024, NW = TH / 64;
-  constexpr int PLANE = BP * 16;
+// The tile of features [f0, f0 + 64): a lane's place in it, one trip of U records per lane, and the flush.
+// seg_hist_lane4_kernel feeds it from the record buffer, seg_hist_lane4_root_kernel from its codes ring.
+template <int BP>
+struct Lane4Tile {
   static_assert(BP == 128 || BP == 256, "four planes of 128 or 256 bins");
-  __shared__ __attribute__((aligned(16))) unsigned long long h[4 * PLANE];  // [4][BP][16]
-  const int b = blockIdx.x, k = b >> 3;
-  const int c = (k / ny) * 8 + (b & 7), fy = k - (k / ny) * ny;
-  if (c >= nwork) return;
-  const int start = a.work[3 * c], len = a.work[3 * c + 1], slot = a.work[3 * c + 2];
-  const int f0 = fy * 64;
-  for (int i = threadIdx.x; i < 4 * PLANE; i += TH) h[i] = 0ull;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, qt = lane >> 4, lq = lane & 15;
-  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  int dw = (f0 >> 2) + lq;
-  const int dmax = (row_bytes >> 2) - 1;
-  dw = dw < dmax ? dw : dmax;
-  const uint8_t* lbase = bins8 + 4 * dw;
-  const uint32_t loff = (uint32_t)lq * 8u;
-  // unconditional record loads reach 4U - 1 records past the chunk end: REC_PAD (64) covers U <= 16
-  static_assert(4 * U <= 64, "record over-read must stay within REC_PAD");
-  // per-quarter vector record loads (scalar-cache records with a 4-way select measured 743.6 vs 671.1 ms per 20
-  // GBDT trees: four selects per item and the lgkmcnt drain of the atomics before every trip)
-  const uint64_t* __restrict__ recp = a.rec + start + qt;
-  for (int i0 = wid * 4 * U; i0 < len; i0 += NW * 4 * U) {
-    uint64_t rc[U];
-#pragma unroll
-    for (int p = 0; p < U; ++p) rc[p] = recp[i0 + 4 * p];
-    if (i0 + 4 * U > len) {
-#pragma unroll
-      for (int p = 0; p < U; ++p)
-        if (i0 + 4 * p + qt >= len) rc[p] = 0ull;
-    }
+  static constexpr int TH = 1024, NW = TH / 64;
+  static constexpr int PLANE = BP * 16;
+  static constexpr int CELLS = 4 * PLANE;  // [4][BP][16]
+  int f0, row_bytes;
+  int qt;  // the lane's item of the wave's four
+  const uint8_t* lbase;
+  uint32_t loff;  // l' << 3
+
+  __device__ __forceinline__ Lane4Tile(const uint8_t* bins8, int row_bytes_, int fy) : f0(fy * 64), row_bytes(row_bytes_) {
+    const int lane = threadIdx.x & 63, lq = lane & 15;
+    qt = lane >> 4;
+    int dw = (f0 >> 2) + lq;
+    const int dmax = (row_bytes >> 2) - 1;
+    dw = dw < dmax ? dw : dmax;
+    lbase = bins8 + 4 * dw;
+    loff = (uint32_t)lq * 8u;
+  }
+
+  // U records per lane (record 0 where the lane has none): U dword gathers, then 4 atomics per record
+  template <int U>
+  __device__ __forceinline__ void trip(unsigned long long* h, const uint64_t (&rc)[U]) const {
     uint32_t x[U];
 #pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t row = (uint32_t)rc[p] & 0x7FFFFFFFu;
-      x[p] = *reinterpret_cast<const uint32_t*>(lbase + (uint64_t)row * (uint64_t)row_bytes);
-    }
+    for (int p = 0; p < U; ++p)
+      x[p] = *reinterpret_cast<const uint32_t*>(lbase + (uint64_t)rec_row(rc[p]) * (uint64_t)row_bytes);
 #pragma unroll
     for (int p = 0; p < U; ++p) {
-      const uint32_t lo = (uint32_t)rc[p], hi = (uint32_t)(rc[p] >> 32);
-      const uint32_t w = __builtin_amdgcn_alignbit(hi, lo, 31) & 0xFFu;
-      const unsigned long long add = ((unsigned long long)(w << (kPackShift - 32)) << 32) +
-                                     (unsigned long long)w * (hi >> 7);
+      const unsigned long long add = rec_addend(rc[p]);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const uint32_t off = (__builtin_amdgcn_ubfe(x[p], 8u * j, 8u) << 7) | loff;  // bin << 7 | l' << 3
@@ -830,18 +812,51 @@ __global__ __launch_bounds__(1024) void seg_hist_lane4_kernel(const SegHistArgs 
       }
     }
   }
-  __syncthreads();
-  for (int cc = threadIdx.x; cc < 4 * PLANE; cc += TH) {
-    const int b_lo = cc & 7, l = (cc >> 3) & 15, j = (cc >> 7) & 3, b_hi = cc >> 9;
-    const int bn = b_hi * 8 + b_lo;
-    const int f = f0 + 4 * l + j;
-    if (bn >= a.B || f >= a.d) continue;
-    const unsigned long long v = h[j * PLANE + bn * 16 + l];
-    if (!v) continue;
-    const unsigned long long cnt = v >> kPackShift;
-    const long long sum = (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)cnt;
-    flush_packed(a, ((int64_t)slot * a.d + f) * a.B + bn, cnt, sum);
+
+  __device__ __forceinline__ void flush(const unsigned long long* h, const SegHistArgs& a, int oslot) const {
+    __syncthreads();
+    for (int cc = threadIdx.x; cc < CELLS; cc += TH) {
+      const int b_lo = cc & 7, l = (cc >> 3) & 15, j = (cc >> 7) & 3, b_hi = cc >> 9;
+      const int bn = b_hi * 8 + b_lo;
+      const int f = f0 + 4 * l + j;
+      if (bn >= a.B || f >= a.d) continue;
+      const unsigned long long v = h[j * PLANE + bn * 16 + l];
+      if (!v) continue;
+      flush_packed(a, ((int64_t)oslot * a.d + f) * a.B + bn, cell_unpack(v));
+    }
   }
+};
+
+template <int BP, int U>
+__global__ __launch_bounds__(1024) void seg_hist_lane4_kernel(const SegHistArgs a, const uint8_t* __restrict__ bins8,
+                                                              int row_bytes, int nwork, int ny) {
+  using Tile = Lane4Tile<BP>;
+  constexpr int NW = Tile::NW;
+  __shared__ __attribute__((aligned(16))) unsigned long long h[Tile::CELLS];
+  const int b = blockIdx.x, k = b >> 3;
+  const int c = (k / ny) * 8 + (b & 7), fy = k - (k / ny) * ny;
+  if (c >= nwork) return;
+  const int start = a.work[3 * c], len = a.work[3 * c + 1], slot = a.work[3 * c + 2];
+  clear_cells<Tile::CELLS>(h);
+  const Tile t(bins8, row_bytes, fy);
+  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  // unconditional record loads reach 4U - 1 records past the chunk end: REC_PAD (64) covers U <= 16
+  static_assert(4 * U <= 64, "record over-read must stay within REC_PAD");
+  // per-quarter vector record loads (scalar-cache records with a 4-way select measured 743.6 vs 671.1 ms per 20
+  // GBDT trees: four selects per item and the lgkmcnt drain of the atomics before every trip)
+  const uint64_t* __restrict__ recp = a.rec + start + t.qt;
+  for (int i0 = wid * 4 * U; i0 < len; i0 += NW * 4 * U) {
+    uint64_t rc[U];
+#pragma unroll
+    for (int p = 0; p < U; ++p) rc[p] = recp[i0 + 4 * p];
+    if (i0 + 4 * U > len) {
+#pragma unroll
+      for (int p = 0; p < U; ++p)
+        if (i0 + 4 * p + t.qt >= len) rc[p] = 0ull;
+    }
+    t.trip(h, rc);
+  }
+  t.flush(h, a, slot);
 }
 
 struct SegPartArgs {
@@ -1002,7 +1017,7 @@ struct CompactArgs {
   float* v0_out;
   float* v1_out;
   uint8_t* w_out;
-  uint64_t* rec_out;  // optional packed records (see CompactWArgs)
+  uint64_t* rec_out;  // optional packed records (packed.h)
   float qs1;
 };
 
@@ -1067,9 +1082,7 @@ __global__ __launch_bounds__(256) void codes_compact_kernel(const CompactArgs a)
     const int pos = (loc != 0xFFu && s_slot[loc] >= 0) ? s_base[loc] + atomicAdd(&s_cnt[loc], 1) : -1;
     if (pos >= 0) {
       if (a.rec_out) {
-        int q1 = (int)rintf(a.v1[r] * a.qs1);
-        q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-        a.rec_out[pos] = (uint64_t)r | ((uint64_t)(c >> 8) << 31) | ((uint64_t)(uint32_t)(q1 + kPackQ) << 39);
+        a.rec_out[pos] = cdna::rec_encode((uint64_t)r, c >> 8, a.v1[r], a.qs1);
       } else {
         a.perm_out[pos] = (int)r;
         a.v1_out[pos] = a.v1[r];
@@ -1083,7 +1096,7 @@ __global__ __launch_bounds__(256) void codes_compact_kernel(const CompactArgs a)
 
 // Node-id twin of codes_compact_kernel for forest levels deeper than the u16 codes reach (binary classification
 // below level 8: up to 512 active nodes per tree): node ids int32 [T][n] (global active index, -1 = done) and
-// the bootstrap weights uint8 [T][n] in, the level's packed item records (row | w << 31 | (q + 2^23) << 39) out,
+// the bootstrap weights uint8 [T][n] in, the level's packed item records (packed.h) out,
 // one segment per built slot -- so the deep levels take the same record histograms (seg_hist_lane10) as the
 // shallow ones instead of the node-id kernel, which re-read every row once per LDS-sized slot group.
 constexpr int kNodeCompactLoc = 1024;  // active nodes per tree
@@ -1158,9 +1171,7 @@ __global__ __launch_bounds__(256) void node_compact_kernel(const NodeCompactArgs
       const int l = local(id[u]);
       if (l < 0) continue;
       const int pos = s_base[l] + atomicAdd(&s_cnt[l], 1);
-      int q1 = (int)rintf(a.v1[r] * a.qs1);
-      q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-      a.rec_out[pos] = (uint64_t)r | ((uint64_t)wt[r] << 31) | ((uint64_t)(uint32_t)(q1 + kPackQ) << 39);
+      a.rec_out[pos] = cdna::rec_encode((uint64_t)r, wt[r], a.v1[r], a.qs1);
     }
   }
 }
@@ -1190,9 +1201,7 @@ struct CompactWArgs {
   float* v0_out;
   float* v1_out;
   uint8_t* w_out;
-  // rec_out != null: one packed record per item instead of perm / v1 / w:
-  // row (31 bits) | weight << 31 (8 bits) | (clamp(rint(v1 * qs1), +-2^23) + 2^23) << 39 (25 bits)
-  uint64_t* rec_out;
+  uint64_t* rec_out;  // != null: one packed record (packed.h) per item instead of perm / v1 / w
   float qs1;
   const int64_t* kstart;  // pass 2, optional: [T][KB] segment start added to the per-wave offsets
 };
@@ -1388,9 +1397,7 @@ __global__ __launch_bounds__(256) void codes_scatter_w_kernel(const CompactWArgs
       if (pos < 0) continue;
       const int64_t r = rb + j * 64 + lane;
       if (a.rec_out) {
-        int q1 = (int)rintf(x1[j] * a.qs1);
-        q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-        a.rec_out[pos] = (uint64_t)r | ((uint64_t)(cc[j] >> 8) << 31) | ((uint64_t)(uint32_t)(q1 + kPackQ) << 39);
+        a.rec_out[pos] = cdna::rec_encode((uint64_t)r, cc[j] >> 8, x1[j], a.qs1);
       } else {
         a.perm_out[pos] = (int)r;
         a.v1_out[pos] = x1[j];
@@ -1476,10 +1483,8 @@ __global__ __launch_bounds__(256) void codes_scatter_q_kernel(const CompactWArgs
       cur += (int)((tot_mine >> (8 * (lane & 3))) & 0xFFu);
     }
     if (pos >= 0) {
-      int q1 = (int)rintf(x1 * a.qs1);
-      q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
       const uint64_t r = (uint64_t)(r_begin + (int64_t)(meta & 0xFFFFu));
-      a.rec_out[pos] = r | ((uint64_t)((meta >> 16) & 0xFFu) << 31) | ((uint64_t)(uint32_t)(q1 + kPackQ) << 39);
+      a.rec_out[pos] = cdna::rec_encode(r, (meta >> 16) & 0xFFu, x1, a.qs1);
     }
   };
   const bool vec = (a.n & 3) == 0 && (reinterpret_cast<uintptr_t>(a.codes) & 7u) == 0 &&
@@ -1626,9 +1631,6 @@ __global__ __launch_bounds__(256) void bins_row_major_kernel(const uint64_t* __r
   }
 }
 
-}  // namespace
-
-namespace {
 // Wide-bin (80 < B <= 256) twin of seg_hist_lane10_root_kernel for boosting (GBDT, one tree per round: every
 // level-0 / level-1 histogram has one built node per tree): the quarter-wave lane4 histogram (64 features per
 // block, XCD-paired feature blocks) fed by per-wave LDS rings of records compacted from the row codes instead
@@ -1641,10 +1643,9 @@ __global__ __launch_bounds__(1024) void seg_hist_lane4_root_kernel(const SegHist
                                                                    const uint16_t* __restrict__ codes,
                                                                    const float* __restrict__ v1, float qs1,
                                                                    const int* __restrict__ sinfo, int slot0) {
-  constexpr int TH = 1024, NW = TH / 64, NI = 4 * U, RING = 128;  // NI - 1 + 64 < RING
-  constexpr int PLANE = BP * 16;
-  static_assert(BP == 128 || BP == 256, "four planes of 128 or 256 bins");
-  __shared__ __attribute__((aligned(16))) unsigned long long h[4 * PLANE];  // [4][BP][16]
+  using Tile = Lane4Tile<BP>;
+  constexpr int NW = Tile::NW, NI = 4 * U, RING = 128;
+  __shared__ __attribute__((aligned(16))) unsigned long long h[Tile::CELLS];
   __shared__ __attribute__((aligned(16))) uint64_t ring[NW][RING];
   const int b = blockIdx.x, k = b >> 3;
   const int c = (k / ny) * 8 + (b & 7), fy = k - (k / ny) * ny;
@@ -1654,89 +1655,13 @@ __global__ __launch_bounds__(1024) void seg_hist_lane4_root_kernel(const SegHist
   const uint32_t node = (uint32_t)sinfo[2 * slot + 1];
   if (!CDNA_DCHECK(r0 >= 0 && len >= 0 && slot >= slot0 && tree >= 0 && node < 0xFFu && (int64_t)r0 + len <= a.n,
                    0x5E86u)) return;
-  const int f0 = fy * 64;
-  for (int i = threadIdx.x; i < 4 * PLANE; i += TH) h[i] = 0ull;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, qt = lane >> 4, lq = lane & 15;
+  clear_cells<Tile::CELLS>(h);
+  const Tile t(bins8, row_bytes, fy);
   const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  int dw = (f0 >> 2) + lq;
-  const int dmax = (row_bytes >> 2) - 1;
-  dw = dw < dmax ? dw : dmax;
-  const uint8_t* lbase = bins8 + 4 * dw;
-  const uint32_t loff = (uint32_t)lq * 8u;
-  const uint16_t* ct = codes + (int64_t)tree * a.n;
-  uint64_t* rg = ring[wid];
-  const int per = ((len + NW - 1) / NW + 63) & ~63;
-  int64_t wr = (int64_t)r0 + (int64_t)wid * per;
-  const int64_t wend = (int64_t)r0 + len < wr + per ? (int64_t)r0 + len : wr + per;
-  uint32_t head = 0u, tail = 0u;
-  uint32_t ncw = 0xFFu;
-  float ny_ = 0.f;
-  auto fetch = [&](int64_t r) {
-    ncw = r < wend ? (uint32_t)ct[r] : 0xFFu;
-    ny_ = r < wend ? v1[r] : 0.f;
-  };
-  fetch(wr + lane);
-  for (;;) {
-    while (tail - head < (uint32_t)NI && wr < wend) {
-      const uint32_t cw = ncw;
-      const float y = ny_;
-      const int64_t r = wr + lane;
-      wr += 64;
-      fetch(wr + lane);
-      const bool has = (cw & 0xFFu) == node && (cw >> 8) != 0u;
-      const uint64_t m = __builtin_amdgcn_ballot_w64(has);
-      if (has) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        int q1 = (int)rintf(y * qs1);
-        q1 = q1 > kPackQ ? kPackQ : (q1 < -kPackQ ? -kPackQ : q1);
-        rg[(tail + rank) & (RING - 1)] =
-            (uint64_t)r | ((uint64_t)(cw >> 8) << 31) | ((uint64_t)(uint32_t)(q1 + kPackQ) << 39);
-      }
-      tail += (uint32_t)__builtin_popcountll(m);
-    }
-    const uint32_t avail = tail - head;
-    if (avail == 0u) break;
-    asm volatile("" ::: "memory");
-    uint64_t rc[U];
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t kk = (uint32_t)(4 * p + qt);
-      rc[p] = kk < avail ? rg[(head + kk) & (RING - 1)] : 0ull;
-    }
-    head += avail < (uint32_t)NI ? avail : (uint32_t)NI;
-    uint32_t x[U];
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t row = (uint32_t)rc[p] & 0x7FFFFFFFu;
-      x[p] = *reinterpret_cast<const uint32_t*>(lbase + (uint64_t)row * (uint64_t)row_bytes);
-    }
-#pragma unroll
-    for (int p = 0; p < U; ++p) {
-      const uint32_t lo = (uint32_t)rc[p], hi = (uint32_t)(rc[p] >> 32);
-      const uint32_t w = __builtin_amdgcn_alignbit(hi, lo, 31) & 0xFFu;
-      const unsigned long long add = ((unsigned long long)(w << (kPackShift - 32)) << 32) +
-                                     (unsigned long long)w * (hi >> 7);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t off = (__builtin_amdgcn_ubfe(x[p], 8u * j, 8u) << 7) | loff;  // bin << 7 | l' << 3
-        atomicAdd(reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(h) + off) + j * PLANE, add);
-      }
-    }
-    asm volatile("" ::: "memory");
-  }
-  __syncthreads();
-  for (int cc = threadIdx.x; cc < 4 * PLANE; cc += TH) {
-    const int b_lo = cc & 7, l = (cc >> 3) & 15, j = (cc >> 7) & 3, b_hi = cc >> 9;
-    const int bn = b_hi * 8 + b_lo;
-    const int f = f0 + 4 * l + j;
-    if (bn >= a.B || f >= a.d) continue;
-    const unsigned long long v = h[j * PLANE + bn * 16 + l];
-    if (!v) continue;
-    const unsigned long long cnt = v >> kPackShift;
-    const long long sum = (long long)(v & ((1ull << kPackShift) - 1ull)) - (long long)kPackQ * (long long)cnt;
-    flush_packed(a, ((int64_t)(slot - slot0) * a.d + f) * a.B + bn, cnt, sum);
-  }
+  CodesRing<RING, NI, false> rq(ring[wid], codes, a.n, v1, qs1, tree, node, r0, len, wid, NW, nullptr);
+  rq.template for_each_trip<U>(t.qt, 4, true,
+                               [&](const uint64_t(&rc)[U]) __attribute__((always_inline)) { t.trip(h, rc); });
+  t.flush(h, a, slot - slot0);
 }
 }  // namespace
 
@@ -1796,12 +1721,8 @@ CDNA_API int cdna_poisson_max_draw(double rate) {
   return k;
 }
 
-// mode bit0: packed (no v0; count | sum in one atomic); bit1: per-row weights wp present;
-// bit4: `perm` holds packed 8-byte item records (row | w << 31 | (q1 + 2^23) << 39; flat kernel only).
-// bit7 (with bit4 and bit2, B <= 256): lane-feature kernels (seg_hist_lane_kernel, B > 80: seg_hist_lane4_kernel).
-// bit9 (packed): 3-class records, sums re-spaced to W1 + 2^32 W2 (SegHistArgs::cls_split).
-// bit2: bins are row-major [n][G] words (seg_hist_flat_kernel when packed and all groups fit 128 KB of LDS,
-// else seg_hist_rm_kernel); bit3: force seg_hist_rm_kernel.
+// mode: SegHistMode bits.  kSegRec without kSegLane: the flat kernel only.  kSegLane: seg_hist_lane8_kernel
+// (B <= 64), seg_hist_lane_kernel (B <= 80), seg_hist_lane4_kernel (B <= 256).
 // work: [nwork][3] {start, len, slot}; grid = nwork x ceil(d / 8).
 CDNA_API int cdna_seg_hist(int mode, const uint64_t* bins, int64_t n, int d, int B, const int* perm, const float* v0p,
                            const float* v1p, const uint8_t* wp, const int* work, int nwork, float qs0, float qs1,
@@ -1811,9 +1732,9 @@ CDNA_API int cdna_seg_hist(int mode, const uint64_t* bins, int64_t n, int d, int
   if (rm_stride != 0 && rm_stride < (d + 7) / 8) return (int)hipErrorInvalidValue;
   SegHistArgs a{bins, n, d, B, perm, v0p, v1p, wp, work, qs0, qs1, out};
   a.rs = rm_stride;
-  a.cls_split = (mode & 512) ? kClsSplit : 0;
-  const bool packed = (mode & 1) != 0, has_w = (mode & 2) != 0;
-  if ((mode & 128) && (mode & 16) && (mode & 4) && packed) {
+  a.cls_split = (mode & kSegCls3) ? kClsSplit : 0;
+  const bool packed = (mode & kSegPacked) != 0, has_w = (mode & kSegHasW) != 0;
+  if ((mode & kSegLane) && (mode & kSegRec) && (mode & kSegRowMajor) && packed) {
     // lane-feature kernel: 128 features per block (4 byte planes of BP >= B bins x 32 lanes, BP KB of LDS);
     // 80 < B <= 256: 64 features per block, a quarter-wave per item (seg_hist_lane4_kernel)
     if (B > 256) return (int)hipErrorInvalidValue;
@@ -1821,7 +1742,7 @@ CDNA_API int cdna_seg_hist(int mode, const uint64_t* bins, int64_t n, int d, int
     a.rec = reinterpret_cast<const uint64_t*>(perm);
     const int row_bytes = (rm_stride ? rm_stride : G) * 8;
     const uint8_t* b8 = reinterpret_cast<const uint8_t*>(bins);
-    if (mode & 256) {
+    if (mode & kSegRows10) {
       // bins rows in the seg10 layout (binize v5 with Gs = -10): six items per wave
       if (d > 100 || B > 40 || row_bytes != 128) return (int)hipErrorInvalidValue;
       auto launch10 = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)nwork), dim3(1024), 0, st, a, b8); };
@@ -1851,9 +1772,9 @@ CDNA_API int cdna_seg_hist(int mode, const uint64_t* bins, int64_t n, int d, int
     launch(seg_hist_lane_kernel<80>);  // 64 < B <= 80 (B <= 64: the quarter-wave lane8 kernel above)
     return (int)hipGetLastError();
   }
-  if ((mode & 16) && !((mode & 4) && packed && (size_t)8 * B * 8 <= 128 * 1024 && !(mode & 8)))
+  if ((mode & kSegRec) && !((mode & kSegRowMajor) && packed && (size_t)8 * B * 8 <= 128 * 1024 && !(mode & kSegForceRm)))
     return (int)hipErrorInvalidValue;
-  if ((mode & 4) && packed && (size_t)8 * B * 8 <= 128 * 1024 && !(mode & 8)) {
+  if ((mode & kSegRowMajor) && packed && (size_t)8 * B * 8 <= 128 * 1024 && !(mode & kSegForceRm)) {
     // lanes over (row, group) pairs; the groups are split over as few blocks as fit 128 KB of LDS
     const int G = (d + 7) / 8;
     int ngb = (128 * 1024) / (8 * B * 8);
@@ -1867,7 +1788,7 @@ CDNA_API int cdna_seg_hist(int mode, const uint64_t* bins, int64_t n, int d, int
                                   (int)lds);
       hipLaunchKernelGGL(kern, dim3((unsigned)nwork, (unsigned)nblk_g), dim3(1024), lds, st, a, bins, G, ngb);
     };
-    if (mode & 16) {  // perm holds packed item records
+    if (mode & kSegRec) {  // perm holds packed item records
       a.rec = reinterpret_cast<const uint64_t*>(perm);
       launch(seg_hist_flat_kernel<true, true>);
     } else if (has_w) {
@@ -1877,7 +1798,7 @@ CDNA_API int cdna_seg_hist(int mode, const uint64_t* bins, int64_t n, int d, int
     }
     return (int)hipGetLastError();
   }
-  if (mode & 4) {  // bins is row-major [n][G]
+  if (mode & kSegRowMajor) {  // bins is row-major [n][G]
     const int G = (d + 7) / 8;
     const int cells_max = 16384 / (packed ? 1 : 2);  // 128 KB of u64 planes
     int ngb = cells_max / (8 * B);

@@ -256,3 +256,18 @@ def test_native_seg_plan_matches_numpy():
                         np.testing.assert_array_equal(w, w_ref)
                         cases += 1
     assert cases > 500
+
+
+def test_rec_encode_decode_round_trip_at_field_extremes():
+    """Packed item records (csrc/kernels/packed.h) at the ends of every field: the top q sets bit 63, so the
+    int64 word is negative and the decode must not sign-extend it into the label."""
+    import itertools
+    rows, w, q = (torch.tensor(c, dtype=torch.int64) for c in zip(*itertools.product(
+        (0, (1 << 31) - 1), (0, 255), (-(1 << 23), 0, 1 << 23))))
+    rec = K.rec_encode(rows, w, q)
+    assert rec.dtype == torch.int64 and len(rec) == 12
+    assert bool((rec[q == (1 << 23)] < 0).all()) and bool((rec[q < (1 << 23)] >= 0).all())
+    r2, w2, q2 = K.rec_decode(rec)
+    assert torch.equal(r2, rows) and torch.equal(w2, w) and torch.equal(q2, q)
+    # narrower inputs encode to the same int64 words
+    assert torch.equal(K.rec_encode(rows.to(torch.int32), w.to(torch.uint8), q.to(torch.int32)), rec)
