@@ -369,6 +369,7 @@ class _TreeClassifierModel(_TreeModelBase):
         names = (self.getRawPredictionCol(), self.getPredictionCol(), self.getProbabilityCol())
         forest, tw = self._forest, self._tree_w
         kind = "counts" if self._counts_raw else "value"
+        self._check_contributions()  # class-output leaves: NotImplementedError when contributionsCol is set
         thresholds = self.getThresholds()
         from .inference import predictor_for
         predictor = predictor_for(self, kind)
@@ -497,6 +498,7 @@ class GBTClassificationModel(_TreeModelBase):
         require_vector(dataset, fc)
         names = (self.getRawPredictionCol(), self.getPredictionCol(), self.getProbabilityCol())
         forest, tw = self._forest, self._tree_w
+        self._check_contributions()
 
         def fn(b, ctx):
             X = b.columns[fc].values
@@ -505,7 +507,12 @@ class GBTClassificationModel(_TreeModelBase):
             raw = torch.stack([-F, F], 1)
             p1 = 1.0 / (1.0 + torch.exp(-2 * F))
             prob = torch.stack([1 - p1, p1], 1)
-            return _append_cls_outputs(b, raw, prob, (F > 0).double(), names)
+            out = _append_cls_outputs(b, raw, prob, (F > 0).double(), names)
+            extra = {}
+            self._contrib_col(b, extra)  # contributions to the margin F
+            for k, v in extra.items():
+                out = out.with_column(k, v)
+            return out
         return dataset._new(MapPlan(dataset._plan, "GBTClassificationModel", fn))
 
 

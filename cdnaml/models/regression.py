@@ -637,7 +637,16 @@ def _num_classes(session, y: torch.Tensor, meta_label: Optional[dict]) -> int:
 
 
 class _TreeModelBase(Model):
-    """Shared prediction + persistence for tree ensembles."""
+    """Shared prediction + persistence for tree ensembles.
+
+    ``contributionsCol`` (model-only output param, off by default): a vector column of numFeatures + 1 doubles per
+    row, the exact path-dependent TreeSHAP contribution of every feature to the row's raw prediction (the margin
+    of a GBTClassifier) and, last, the bias; a row's contributions sum to its raw prediction.  Single-output
+    ensembles only: DecisionTree / RandomForest classification models raise NotImplementedError."""
+    _params = {
+        "contributionsCol": ("Per-feature TreeSHAP contributions (+ bias) column name; empty: not computed.", "",
+                             TC.toString),
+    }
 
     def __init__(self, forest: Optional[Forest] = None, numFeatures: int = 0, tree_weights=None):
         super().__init__()
@@ -725,6 +734,28 @@ class _TreeModelBase(Model):
             leaves = self._forest.predict_leaf_index(X).double().to(X.device)
             out_cols[lc] = ColumnData(leaves, T.VectorUDT())
 
+    def _check_contributions(self) -> str:
+        """The contributions column name ("": off); raises for ensembles TreeSHAP does not cover."""
+        cc = self.getContributionsCol()
+        if cc and self._forest.K != 1:
+            raise NotImplementedError(
+                f"{type(self).__name__}: contributionsCol needs a single-output ensemble (regression trees or GBT "
+                f"margins); this model's leaves hold {self._forest.K} class outputs")
+        return cc
+
+    def _contrib_col(self, b, out_cols):
+        cc = self.getContributionsCol()
+        if cc:
+            X = b.columns[self.getFeaturesCol()].values
+            phi = self._forest.shap_values(X, self._tree_w, [getattr(self, "_base", 0.0)])
+            out_cols[cc] = ColumnData(phi, T.VectorUDT())
+
+    def featureContributions(self, dataset, contributionsCol: str = "contributions"):
+        """``transform(dataset)`` with the TreeSHAP contributions column on (``contributionsCol`` as set on the
+        model, else the given name)."""
+        cc = self.getContributionsCol() or contributionsCol
+        return self.copy({self.contributionsCol: cc}).transform(dataset)
+
 
 class _TreeRegressorModel(_TreeModelBase):
     _base = 0.0
@@ -733,6 +764,7 @@ class _TreeRegressorModel(_TreeModelBase):
         fc, pc = self.getFeaturesCol(), self.getPredictionCol()
         require_vector(dataset, fc)
         forest, tw, base = self._forest, self._tree_w, self._base
+        self._check_contributions()
 
         from .inference import predictor_for
         predictor = predictor_for(self, "value", [base])  # forest uploaded once; recurring buffers graph-replayed
@@ -743,6 +775,7 @@ class _TreeRegressorModel(_TreeModelBase):
                 torch.zeros(0, dtype=torch.float64, device=X.device)
             out = {pc: ColumnData(p, T.DoubleType())}
             self._leaf_col(b, out)
+            self._contrib_col(b, out)
             nb = b
             for k, v in out.items():
                 nb = nb.with_column(k, v)

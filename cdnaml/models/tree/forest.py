@@ -233,6 +233,7 @@ class Forest:
         self._heap_np = None  # (struct [T, 2^(D+1)-1, 2] int32, leaf values [T, 2^(D+1)-1] f64, D) built by
         # ForestTrainer.train (Forest.heap_struct's arrays), or None
         self._fit_bins: Optional[FitBins] = None
+        self._shap = {}       # shap_paths' cache (never pickled)
 
     def settle(self) -> None:
         """Run the deferred bookkeeping (idempotent; a no-op when nothing is pending).
@@ -257,6 +258,7 @@ class Forest:
         st["_settling"] = None
         st.pop("_settle_lock", None)
         st.pop("_fit_bins", None)   # device bins of the training tensor: process-local
+        st.pop("_shap", None)       # the flattened paths (shap_paths): rebuilt on demand
         return st
 
     def __setstate__(self, st):
@@ -561,22 +563,140 @@ class Forest:
         return K.tree_predict(X, nodes, roots, tw, vals, masks, self.K, b)
 
     def predict_leaf_index(self, X: torch.Tensor) -> torch.Tensor:
-        """Host reference traversal returning leaf ids [n, T] (small inputs only)."""
-        Xn = X.double().cpu().numpy()
-        out = np.zeros((Xn.shape[0], len(self.roots)), dtype=np.int64)
-        for t, r in enumerate(self.roots):
-            for i in range(Xn.shape[0]):
-                j = r
-                while self.feat[j] >= 0:
-                    x = Xn[i, self.feat[j]]
-                    if self.is_cat[j]:
-                        c = int(x)
-                        go_left = 0 <= c < 256 and (int(self.catmask[j][c >> 5]) >> (c & 31)) & 1
+        """Leaf ids [n, T] int64: the global node id each row reaches in each tree, walked on X's device with the
+        predictors' split decisions (K.tree_leaf_index)."""
+        nodes, roots, _, masks = self.device_arrays(X.device)
+        return K.tree_leaf_index(X, nodes, roots, masks).long()
+
+    # ----------------------------------------------------------- TreeSHAP
+    def shap_paths(self, binned: bool = False) -> dict:
+        """The forest's root-to-leaf paths flattened for K.tree_shap (host numpy arrays, cached): trees in
+        ascending order, leaves in left-first DFS order.
+
+        Per path: ``hdr`` int32 [P, 4] = {first step, steps, first slot, slots}, ``tree`` / ``leaf`` (node id) /
+        ``val`` (fp64 leaf value) and ``pz`` (the product of its slots' z).  Per step: ``steps`` int32 [S, 4] =
+        {feature code, payload, 1 if the path goes left, slot within the path}; the code is the feature of a
+        numeric split (payload: the fp32 threshold's bits, or the node's bin when ``binned``) and -(feature + 2)
+        of a categorical one (payload: offset of its uint32[8] mask in ``masks``).  Per slot (the steps of a path
+        on one feature, merged): ``slot_feat``, ``slot_z`` (product of cover(child) / cover(parent) over its
+        steps, the cover being ``weight``) and ``slot_rz`` = 1 / z.  ``max_slots``: the largest slot count.
+
+        Only single-output forests; a zero-cover child of an internal node or a path of more than 32 slots is a
+        ValueError."""
+        if self.K != 1:
+            raise NotImplementedError("TreeSHAP contributions are implemented for single-output forests only "
+                                      f"(this forest has {self.K} outputs per leaf)")
+        L = self.lists()
+        key = (bool(binned), len(L["feat"]), len(self.roots))
+        cache = self.__dict__.setdefault("_shap", {})
+        if key in cache:
+            return cache[key]
+        feat, left, right = L["feat"].array().tolist(), L["left"].array().tolist(), L["right"].array().tolist()
+        cover, is_cat = L["weight"].array().tolist(), L["is_cat"].array().tolist()
+        value = L["value"].array()[:, 0].tolist()
+        if binned:
+            payload = L["bin"].array().astype(np.int64).tolist()
+        else:
+            payload = L["thr"].array().astype(np.float32).view(np.int32).tolist()
+        mask_off, masks = {}, []
+        hdr, p_tree, p_leaf, p_val, p_pz = [], [], [], [], []
+        steps, s_feat, s_z = [], [], []
+        for t, root in enumerate(self.roots):
+            stack = [(int(root), ())]
+            while stack:
+                i, path = stack.pop()
+                f = feat[i]
+                if f >= 0:
+                    kids = []
+                    for c, go_left in ((left[i], 1), (right[i], 0)):
+                        if not cover[c] > 0.0 or not cover[i] > 0.0:
+                            raise ValueError(f"TreeSHAP: child {c} of node {i} (tree {t}) has zero cover")
+                        if is_cat[i]:
+                            if i not in mask_off:
+                                mask_off[i] = len(masks)
+                                masks.append(L["catmask"].array()[i].view(np.int32))
+                            st = (-(f + 2), mask_off[i], go_left, f, cover[c] / cover[i])
+                        else:
+                            st = (f, payload[i], go_left, f, cover[c] / cover[i])
+                        kids.append((c, path + (st,)))
+                    stack.extend(reversed(kids))  # left first
+                    continue
+                slots, zs = {}, []
+                s0 = len(steps)
+                for code, pay, go_left, f_, frac in path:
+                    k = slots.get(f_)
+                    if k is None:
+                        k = slots[f_] = len(zs)
+                        zs.append(frac)
                     else:
-                        go_left = x <= self.thr[j]
-                    j = self.left[j] if go_left else self.right[j]
-                out[i, t] = j
-        return torch.from_numpy(out)
+                        zs[k] = zs[k] * frac
+                    steps.append((code, pay, go_left, k))
+                if len(zs) > 32:
+                    raise ValueError(f"TreeSHAP: the path to leaf {i} (tree {t}) splits on {len(zs)} distinct "
+                                     "features; at most 32 are supported")
+                hdr.append((s0, len(path), len(s_feat), len(zs)))
+                s_feat.extend(slots.keys())
+                s_z.extend(zs)
+                pz = 1.0
+                for z in zs:
+                    pz = pz * z
+                p_tree.append(t)
+                p_leaf.append(i)
+                p_val.append(value[i])
+                p_pz.append(pz)
+        z = np.asarray(s_z, dtype=np.float64)
+        out = {
+            "hdr": np.asarray(hdr, dtype=np.int32).reshape(-1, 4),
+            "tree": np.asarray(p_tree, dtype=np.int64), "leaf": np.asarray(p_leaf, dtype=np.int64),
+            "val": np.asarray(p_val, dtype=np.float64), "pz": np.asarray(p_pz, dtype=np.float64),
+            "steps": np.asarray(steps, dtype=np.int32).reshape(-1, 4),
+            "slot_feat": np.asarray(s_feat, dtype=np.int32), "slot_z": z, "slot_rz": 1.0 / z,
+            "masks": np.concatenate(masks).astype(np.int32) if masks else np.zeros(8, np.int32),
+            "max_slots": max((h[3] for h in hdr), default=0),
+        }
+        if any(k[0] != "dev" and k[1:] != key[1:] for k in cache):
+            cache.clear()  # tables of an earlier state of the forest (a boosted forest grows)
+        cache[key] = out
+        return out
+
+    def shap_bias(self, tree_w: np.ndarray, base=None, binned: bool = False) -> float:
+        """base + sum_t tree_w[t] * E_t, E_t the cover-weighted mean leaf value of tree t (summed in path order)."""
+        sp = self.shap_paths(binned)
+        tw = np.asarray(tree_w, np.float64).reshape(-1)
+        b = 0.0 if base is None else float(np.asarray(base, np.float64).reshape(-1)[0])
+        for v, pz in zip((tw[sp["tree"]] * sp["val"]).tolist(), sp["pz"].tolist()):
+            b = b + v * pz
+        return b
+
+    def shap_values(self, X_or_bins: torch.Tensor, tree_w: np.ndarray, base=None, binned: bool = False,
+                    d: Optional[int] = None, phi: str = "auto", with_margin: bool = False):
+        """Path-dependent TreeSHAP contributions [n, d + 1] fp64 (XGBoost's ``pred_contribs``): column f < d is
+        the exact Shapley value of feature f under the trees' cover-weighted conditional expectation, column d
+        the bias ``shap_bias``; every row sums to ``predict(X, tree_w, base)``.
+
+        ``X_or_bins``: the feature rows [n, d], or with ``binned`` the uint8 bins [G, n, 8] of K.binize (then
+        ``d`` is required) tested against the nodes' bins as the XGBoost models predict.  Single-output forests
+        only (NotImplementedError otherwise).
+
+        ``with_margin``: return (phi, margin), margin [n] fp64 = base + sum_t tree_w[t] * the leaf value the row
+        reaches, accumulated by the same pass from the leaves themselves (not from phi)."""
+        sp = self.shap_paths(binned)
+        dev = X_or_bins.device
+        d = int(X_or_bins.shape[1] if not binned else d)
+        if len(sp["slot_feat"]) and int(sp["slot_feat"].max()) >= d:
+            raise ValueError(f"the forest splits on feature {int(sp['slot_feat'].max())} but the rows have {d}")
+        dkey = ("dev", str(dev), bool(binned))  # the device tables live and die with the flattening (_shap)
+        tabs = self._shap.get(dkey)
+        if tabs is None or tabs[0] is not sp:
+            tabs = (sp, dict(zip(("hdr", "steps", "slot_feat", "slot_z", "slot_rz", "masks"),
+                                 K.upload(dev, sp["hdr"], sp["steps"], sp["slot_feat"], sp["slot_z"],
+                                          sp["slot_rz"], sp["masks"]))))
+            self._shap[dkey] = tabs
+        tw = np.asarray(tree_w, np.float64).reshape(-1)
+        pv, = K.upload(dev, tw[sp["tree"]] * sp["val"])
+        b0 = 0.0 if base is None else float(np.asarray(base, np.float64).reshape(-1)[0])
+        return K.tree_shap(X_or_bins, tabs[1], pv, self.shap_bias(tree_w, base, binned), d, sp["max_slots"],
+                           binned=binned, phi=phi, margin_base=b0 if with_margin else None)
 
     # ----------------------------------------------------------- persistence
     def state(self, prefix="forest_"):

@@ -41,8 +41,8 @@ from .forest import Forest, freeze_cut
 FUSED_TUNING = os.environ.get("CDNAML_FUSED_TUNING", "1") != "0"
 
 _VARYING = ("numTrees", "maxDepth")
-_IGNORED = ("predictionCol", "rawPredictionCol", "probabilityCol", "varianceCol", "leafCol", "thresholds",
-            "checkpointInterval", "cacheNodeIds", "maxMemoryInMB")
+_IGNORED = ("predictionCol", "rawPredictionCol", "probabilityCol", "varianceCol", "leafCol", "contributionsCol",
+            "pred_contrib_col", "thresholds", "checkpointInterval", "cacheNodeIds", "maxMemoryInMB")
 
 
 def estimator_kind(est) -> Optional[Tuple[str, bool]]:

@@ -48,6 +48,8 @@ _XGB = {
     "predictionCol": ("prediction column name", "prediction", TC.toString),
     "weightCol": ("instance weight column name", None, TC.toString),
     "baseMarginCol": ("column holding per-row base margins", None, TC.toString),
+    "pred_contrib_col": ("output column of per-feature TreeSHAP contributions to the margin (+ bias); unset: not "
+                         "computed", None, TC.toString),
     "validationIndicatorCol": ("boolean column marking validation rows (early stopping)", None, TC.toString),
     "n_estimators": ("number of boosting rounds", 100, TC.toInt),
     "learning_rate": ("boosting learning rate (eta)", 0.3, TC.toFloat),
@@ -345,17 +347,41 @@ class _XgbModelBase(Model):
         nz = np.nonzero(imp)[0]
         return SparseVector(self._numFeatures, nz.tolist(), imp[nz].tolist())
 
-    def _margins(self, X: torch.Tensor) -> torch.Tensor:
-        """Binned prediction: missing values follow each node's learned default direction."""
-        n = X.shape[0]
+    def _bins(self, X: torch.Tensor) -> torch.Tensor:
+        """The rows cut into the fit's uint8 bins (missing values -> bin 0 inside the kernel)."""
         dev = X.device
         key = str(dev)
         if key not in self._dev:
             thr = torch.from_numpy(self._thr.astype(np.float32)).to(dev)
             self._dev[key] = (thr, torch.from_numpy(self._nthr).to(dev))
         thr, nthr = self._dev[key]
-        Xf = X.float()
-        bins = K.binize(Xf, thr, nthr, missing=float(self.getMissing()))  # missing -> bin 0 inside the kernel
+        return K.binize(X.float(), thr, nthr, missing=float(self.getMissing()))
+
+    def _check_contributions(self) -> Optional[str]:
+        """The contributions column name (None / "": off); raises for multi-output boosters."""
+        cc = self.getOrDefault("pred_contrib_col")
+        if cc and self._n_out != 1:
+            raise NotImplementedError(
+                f"{type(self).__name__}: pred_contrib_col needs a single-output booster; this model boosts "
+                f"{self._n_out} outputs per round (multi:softprob)")
+        return cc
+
+    def _contributions(self, bins: torch.Tensor):
+        """(phi, margin): phi [n, numFeatures + 1] fp64, the TreeSHAP contributions to the margin (log space for
+        count:poisson, as XGBoost's pred_contribs) over the bins the margins are predicted from -- eta as tree
+        weights, the base margin as base, the last column the bias -- and margin [n] fp64, the margin itself
+        summed in fp64 from the leaves by the same pass.  A transform with ``pred_contrib_col`` set emits its
+        prediction columns from this fp64 margin, so that the contributions of a row sum to the margin it reports
+        (XGBoost's contract); it differs from ``_margins``' fp32 sum by that sum's rounding only."""
+        T_ = len(self._forest.roots)
+        return self._forest.shap_values(bins, np.full(T_, float(self.getLearning_rate())), [self._base],
+                                        binned=True, d=self._numFeatures, with_margin=True)
+
+    def _margins(self, X: torch.Tensor) -> torch.Tensor:
+        """Binned prediction: missing values follow each node's learned default direction."""
+        n = X.shape[0]
+        dev = X.device
+        bins = self._bins(X)
         eta = self.getLearning_rate()
         F = torch.full((n, self._n_out), self._base, dtype=torch.float32, device=dev)
         if dev.type == "cpu":
@@ -391,16 +417,23 @@ class XgboostRegressorModel(_XgbModelBase):
     def _transform(self, dataset):
         fc, pc = self.getFeaturesCol(), self.getPredictionCol()
         require_vector(dataset, fc)
+        cc = self._check_contributions()
 
         def fn(b, ctx):
             X = b.columns[fc].values
-            if X.shape[0] == 0:
+            phi = None
+            if cc:
+                phi, p = self._contributions(self._bins(X))
+            elif X.shape[0] == 0:
                 p = torch.zeros(0, dtype=torch.float64, device=X.device)
             else:
                 p = self._margins(X)[:, 0].double()
-                if self._objective == "count:poisson":
-                    p = torch.exp(p)
-            return b.with_column(pc, ColumnData(p, T.DoubleType()))
+            if self._objective == "count:poisson":
+                p = torch.exp(p)
+            nb = b.with_column(pc, ColumnData(p, T.DoubleType()))
+            if cc:
+                nb = nb.with_column(cc, ColumnData(phi, T.VectorUDT()))
+            return nb
         return dataset._new(MapPlan(dataset._plan, f"XgboostRegressorModel -> {pc}", fn))
 
 
@@ -485,10 +518,15 @@ class XgboostClassifierModel(_XgbModelBase):
         fc = self.getFeaturesCol()
         require_vector(dataset, fc)
         rc, prc, pc = self.getRawPredictionCol(), self.getProbabilityCol(), self.getPredictionCol()
+        cc = self._check_contributions()
 
         def fn(b, ctx):
             X = b.columns[fc].values
-            if X.shape[0] == 0:
+            phi = None
+            if cc:  # single output: the fp64 margin of the contributions' pass, columns kept in fp64
+                phi, F = self._contributions(self._bins(X))
+                F = F[:, None]
+            elif X.shape[0] == 0:
                 F = torch.zeros((0, self._n_out), dtype=torch.float32, device=X.device)
             else:
                 F = self._margins(X)
@@ -502,9 +540,11 @@ class XgboostClassifierModel(_XgbModelBase):
             pred = torch.argmax(prob, 1).double()
             nb = b
             if rc:
-                nb = nb.with_column(rc, ColumnData(raw.float(), T.VectorUDT()))
+                nb = nb.with_column(rc, ColumnData(raw if cc else raw.float(), T.VectorUDT()))
             if prc:
-                nb = nb.with_column(prc, ColumnData(prob.float(), T.VectorUDT()))
+                nb = nb.with_column(prc, ColumnData(prob if cc else prob.float(), T.VectorUDT()))
+            if cc:
+                nb = nb.with_column(cc, ColumnData(phi, T.VectorUDT()))
             return nb.with_column(pc, ColumnData(pred, T.DoubleType()))
         return dataset._new(MapPlan(dataset._plan, "XgboostClassifierModel", fn))
 

@@ -190,6 +190,13 @@ _SIGS = {
                               c_double, c_void_p, c_int, c_int, c_void_p], c_int),
     "cdna_tree_predict_heap": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                 c_double, c_void_p, c_void_p, c_int, c_void_p], c_int),
+    "cdna_tree_shap_lds_bytes": ([c_int, c_int], c_int64),
+    "cdna_tree_shap_lds_budget": ([], c_int64),
+    "cdna_tree_shap": ([c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                        c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_void_p, c_int, c_void_p, c_double,
+                        c_void_p, c_void_p], c_int),
+    "cdna_tree_leaf_index": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                              c_void_p], c_int),
     "cdna_sample_gather": ([c_void_p, c_int64, c_int64, c_int, c_uint64, c_uint64, c_uint32, c_double, c_void_p,
                             c_void_p, c_int64, c_void_p, c_void_p], c_int),
     "cdna_fill_chunk": ([c_void_p, c_int, c_int64, c_int, c_int, c_int64], c_int64),

@@ -1217,33 +1217,188 @@ def tree_predict(X: torch.Tensor, nodes: torch.Tensor, roots: torch.Tensor, tree
     vals = values.double().cpu()
     tw = tree_w.double().cpu()
     mk = masks.long().cpu() & 0xFFFFFFFF
-    rows = torch.arange(n)
 
     def contrib(t):
-        cur = torch.full((n,), int(roots[t]), dtype=torch.long)
-        for _ in range(64):
-            nv = nd[cur]
-            internal = nv[:, 0] != -1
-            if not internal.any():
-                break
-            f = nv[:, 0]
-            cont = f >= 0
-            fi = torch.where(cont, f, -f - 2).clamp(min=0)
-            x = Xf[rows, fi]
-            thr = nv[:, 1].to(torch.int32).view(torch.float32)
-            c = x.to(torch.int64)
-            okc = (c >= 0) & (c < 256)
-            cc = c.clamp(0, 255)
-            moff = torch.where(f <= -2, nv[:, 1], torch.zeros_like(f)).clamp(min=0)
-            words = mk[(moff * 8 + (cc >> 5))] if mk.numel() else torch.zeros_like(cc)
-            catleft = okc & ((words >> (cc & 31)) & 1).bool()
-            left = torch.where(cont, x <= thr, catleft)
-            nxt = torch.where(left, nv[:, 2], nv[:, 3])
-            cur = torch.where(internal, nxt, cur)
+        cur = _walk_to_leaf(Xf, nd, mk, int(roots[t]))
         off = nd[cur][:, 1]
         idx = off[:, None] + torch.arange(K)[None, :]
         return vals[idx] * tw[t]
     return ordered_tree_sum(contrib, T, n, K, base).to(X.device)
+
+
+def _raw_left(x: torch.Tensor, f: torch.Tensor, payload: torch.Tensor, mk: torch.Tensor) -> torch.Tensor:
+    """The predictors' decision on raw fp32 values ``x`` for packed node codes ``f`` (trees.hip): numeric (f >= 0)
+    left iff x <= the fp32 threshold whose bits are ``payload`` (NaN goes right); categorical (f <= -2) left iff
+    the bit (int)x of the mask at offset ``payload`` is set, out of [0, 256) goes right."""
+    cont = f >= 0
+    thr = payload.to(torch.int32).view(torch.float32)
+    c = x.to(torch.int64)
+    okc = (c >= 0) & (c < 256)
+    cc = c.clamp(0, 255)
+    moff = torch.where(f <= -2, payload, torch.zeros_like(payload)).clamp(min=0)
+    words = mk[(moff * 8 + (cc >> 5))] if mk.numel() else torch.zeros_like(cc)
+    catleft = okc & ((words >> (cc & 31)) & 1).bool()
+    return torch.where(cont, x <= thr, catleft)
+
+
+def _walk_to_leaf(Xf: torch.Tensor, nd: torch.Tensor, mk: torch.Tensor, root: int) -> torch.Tensor:
+    """Node id [n] (int64) each fp32 row of ``Xf`` reaches from ``root`` in the packed int64 node table ``nd``."""
+    n = Xf.shape[0]
+    rows = torch.arange(n)
+    cur = torch.full((n,), root, dtype=torch.long)
+    for _ in range(64):
+        nv = nd[cur]
+        internal = nv[:, 0] != -1
+        if not internal.any():
+            break
+        f = nv[:, 0]
+        fi = torch.where(f >= 0, f, -f - 2).clamp(min=0)
+        left = _raw_left(Xf[rows, fi], f, nv[:, 1], mk)
+        nxt = torch.where(left, nv[:, 2], nv[:, 3])
+        cur = torch.where(internal, nxt, cur)
+    return cur
+
+
+# -------------------------------------------------------------------- K21
+def tree_leaf_index(X: torch.Tensor, nodes: torch.Tensor, roots: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
+    """int32 [n, T]: the global node id of the leaf each row reaches in each tree, with ``tree_predict``'s node
+    table and split decisions (shap.hip tree_leaf_index_kernel; on cpu ``tree_predict``'s walk)."""
+    n, d = X.shape
+    T = roots.numel()
+    if _native(X):
+        X = X.float()
+        X = X if X.stride(1) == 1 else X.contiguous()
+        out = torch.empty((n, T), dtype=torch.int32, device=X.device)
+        if n and T:
+            m = masks.int().contiguous() if masks.numel() else torch.zeros(8, dtype=torch.int32, device=X.device)
+            _lib.check(_lib.lib().cdna_tree_leaf_index(_ptr(X), n, d, X.stride(0), _ptr(nodes.int().contiguous()),
+                                                       _ptr(roots.int().contiguous()), T, _ptr(m), _ptr(out),
+                                                       _stream(X.device)), "cdna_tree_leaf_index")
+        return out
+    Xf = X.float().cpu()
+    nd = nodes.long().cpu()
+    mk = masks.long().cpu() & 0xFFFFFFFF
+    out = torch.empty((n, T), dtype=torch.int32)
+    for t in range(T):
+        out[:, t] = _walk_to_leaf(Xf, nd, mk, int(roots[t])).int()
+    return out.to(X.device)
+
+
+SHAP_MAX_SLOTS = 32
+# Where a wave's phi tile accumulates: "global" (a [d][65] fp64 tile of scratch per block) or "lds" (while the tile
+# fits the CU's LDS, else global).  Measured at 1e6 x 100 (profiles/r7/tree_shap.md): the LDS tile allows 2-3 waves
+# per CU and the path loops are latency-bound, so the global tile with 16 blocks per CU is 2.2-2.6x faster.
+SHAP_PHI = "global"
+SHAP_GRID_LDS = 8192     # blocks (one wave each, grid-stride over 64-row tiles)
+SHAP_GRID_GLOBAL = 4096  # 16 per CU; 8192 measured the same, 1024 1.3-2.1x slower
+SHAP_SCRATCH_BYTES = 256 << 20  # cap of the global arrangement's scratch (fewer blocks at large d)
+
+
+def tree_shap(X: torch.Tensor, paths: Dict[str, torch.Tensor], pv: torch.Tensor, bias: float, d: int,
+              max_slots: int, binned: bool = False, phi: str = "auto", margin_base: Optional[float] = None):
+    """Exact path-dependent TreeSHAP (Lundberg et al. 2018, Algorithm 2, per leaf path) -> fp64 [n, d + 1].
+
+    With ``margin_base`` the result is (phi, margin): margin fp64 [n] = margin_base + the ``pv`` of the leaf the row
+    reaches in every tree, added in path order -- the ensemble's raw prediction in fp64 from the same decisions,
+    summed independently of the contributions.
+
+    ``paths``: the tables of ``Forest.shap_paths`` on X's device (hdr, steps, slot_feat, slot_z, slot_rz, masks);
+    ``pv`` fp64 [P]: tree weight * leaf value per path; column d of the result is ``bias``.  ``X``: fp32 rows
+    [n, d], or with ``binned`` the uint8 bins [G, n, 8] of ``binize`` tested against node bins.  Every row's sums
+    are made in (path, slot) order with each product rounded before it is added, on the device (shap.hip
+    tree_shap_kernel) as in the cpu path below, which is vectorised over the rows."""
+    if max_slots > SHAP_MAX_SLOTS:
+        raise ValueError(f"TreeSHAP: {max_slots} distinct features on one path; at most {SHAP_MAX_SLOTS}")
+    if binned:
+        G, n, _ = X.shape
+        assert X.dtype == torch.uint8 and d <= 8 * G, (X.dtype, d, G)
+    else:
+        n = X.shape[0]
+        assert X.shape[1] == d, (tuple(X.shape), d)
+    hdr, steps = paths["hdr"], paths["steps"]
+    P = hdr.shape[0]
+    if _native(X):
+        out = torch.empty((n, d + 1), dtype=torch.float64, device=X.device)
+        margin = None if margin_base is None else torch.empty(n, dtype=torch.float64, device=X.device)
+        if n == 0:
+            return out if margin is None else (out, margin)
+        if not binned:
+            X = X.float()
+            X = X if X.stride(1) == 1 else X.contiguous()
+        else:
+            X = X.contiguous()
+        L = _lib.lib()
+        mode = SHAP_PHI if phi == "auto" else phi
+        assert mode in ("lds", "global"), mode
+        if mode == "lds" and L.cdna_tree_shap_lds_bytes(d, int(binned)) > L.cdna_tree_shap_lds_budget():
+            mode = "global"  # any d: beyond what LDS holds the same kernel accumulates in its global tile
+        tiles = (n + 63) // 64
+        grid = min(tiles, SHAP_GRID_LDS) if mode == "lds" else \
+            min(tiles, SHAP_GRID_GLOBAL, max(256, SHAP_SCRATCH_BYTES // (d * 65 * 8)))
+        scratch = None if mode == "lds" else torch.empty(grid * d * 65, dtype=torch.float64, device=X.device)
+        _lib.check(L.cdna_tree_shap(_ptr(X), int(binned), n, d, 0 if binned else X.stride(0), _ptr(hdr), P,
+                                    _ptr(steps), _ptr(paths["slot_feat"]), _ptr(paths["slot_z"]),
+                                    _ptr(paths["slot_rz"]), _ptr(pv), _ptr(paths["masks"]), float(bias),
+                                    int(max_slots), int(mode == "lds"), _ptr(scratch), grid, _ptr(out),
+                                    0.0 if margin is None else float(margin_base), _ptr(margin),
+                                    _stream(X.device)), "cdna_tree_shap")
+        return out if margin is None else (out, margin)
+    out = torch.zeros((n, d + 1), dtype=torch.float64)
+    out[:, d] = float(bias)
+    margin = torch.full((n,), 0.0 if margin_base is None else float(margin_base), dtype=torch.float64)
+
+    def result():
+        return out.to(X.device) if margin_base is None else (out.to(X.device), margin.to(X.device))
+    if n == 0:
+        return result()
+    Xv = bins_to_matrix(X, d).long() if binned else X.float().cpu()
+    mk = paths["masks"].long() & 0xFFFFFFFF
+    hd, stp = hdr.tolist(), steps.long()
+    sfeat, sz, srz, pvl = paths["slot_feat"].tolist(), paths["slot_z"].double(), paths["slot_rz"].double(), \
+        pv.double().tolist()
+    inv = [0.0] + [1.0 / i for i in range(1, SHAP_MAX_SLOTS + 2)]
+    for p, (s0, ns, k0, m) in enumerate(hd):
+        if m == 0:
+            margin += pvl[p]  # a single-leaf tree: every row reaches it
+            continue
+        on = torch.ones((m, n), dtype=torch.bool)
+        for s in range(s0, s0 + ns):
+            code, pay, go_left, slot = stp[s].tolist()
+            f = code if code >= 0 else -code - 2
+            if binned:
+                b = Xv[:, f]
+                left = (b <= pay) if code >= 0 else ((mk[pay * 8 + (b >> 5)] >> (b & 31)) & 1).bool()
+            else:
+                left = _raw_left(Xv[:, f], torch.full((n,), code), torch.full((n,), pay), mk)
+            on[slot] &= left == bool(go_left)
+        margin += on.all(0).double() * pvl[p]  # the rows that reach this path's leaf
+        o = on.double()
+        z = sz[k0:k0 + m]
+        pw = torch.zeros((m + 1, n), dtype=torch.float64)
+        pw[0] = 1.0
+        for k in range(m):  # extend by slot k: elementwise the device loop j = l-1 .. 0
+            l_ = k + 1
+            rl = inv[l_ + 1]
+            c1 = torch.tensor([(j + 1) * rl for j in range(l_)], dtype=torch.float64)[:, None]
+            c2 = torch.tensor([(l_ - j) * rl for j in range(l_)], dtype=torch.float64)[:, None]
+            old = pw[:l_].clone()
+            pw[:l_] = (z[k] * old) * c2
+            pw[1:l_ + 1] = pw[1:l_ + 1] + (o[k] * old) * c1
+        mp1, rm1 = float(m + 1), inv[m + 1]
+        zc = z[:, None]
+        nxt = pw[m].expand(m, n).clone()
+        tot1 = torch.zeros((m, n), dtype=torch.float64)
+        tot0 = torch.zeros((m, n), dtype=torch.float64)
+        for j in range(m - 1, -1, -1):  # the unwound sums of all m slots at once
+            tmp = nxt * (mp1 * inv[j + 1])
+            tot1 = tot1 + tmp
+            nxt = pw[j] - (tmp * zc) * ((m - j) * rm1)
+            tot0 = tot0 + pw[j] * (mp1 * inv[m - j])
+        tot0 = tot0 * srz[k0:k0 + m, None]
+        c = (torch.where(on, tot1, tot0) * (o - zc)) * pvl[p]
+        for k in range(m):
+            out[:, sfeat[k0 + k]] += c[k]
+    return result()
 
 
 def predict_binned_add(bins: torch.Tensor, nodes: torch.Tensor, root: int, values: torch.Tensor,
