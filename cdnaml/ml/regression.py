@@ -1,3 +1,5 @@
 from ..models.regression import (DecisionTreeRegressionModel, DecisionTreeRegressor, GBTRegressionModel,  # noqa: F401
-                                 GBTRegressor, IsotonicRegression, IsotonicRegressionModel, LinearRegression,
+                                 GBTRegressor, GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
+                                 GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary,
+                                 IsotonicRegression, IsotonicRegressionModel, LinearRegression,
                                  LinearRegressionModel, RandomForestRegressionModel, RandomForestRegressor)

@@ -1154,3 +1154,452 @@ class IsotonicRegressionModel(Model):
 
     def _load_state(self, extra, tensors, stages):
         self._b, self._p = tensors["b"].numpy(), tensors["p"].numpy()
+
+
+# ================================================= GeneralizedLinearRegression
+# family -> (canonical link, links Spark accepts)
+_GLM_LINKS = {
+    "gaussian": ("identity", ("identity", "log", "inverse")),
+    "binomial": ("logit", ("logit", "probit", "cloglog")),
+    "poisson": ("log", ("log", "identity", "sqrt")),
+    "gamma": ("inverse", ("inverse", "identity", "log")),
+}
+_GLM_POWER_LINKS = {0.0: "log", 1.0: "identity", -1.0: "inverse", 0.5: "sqrt"}
+_GLM_POWER_FAMILIES = {0.0: "gaussian", 1.0: "poisson", 2.0: "gamma"}
+
+_GLM_PARAMS = dict(_PRED, **{
+    "family": ("The name of family which is a description of the error distribution to be used in the model. "
+               "Supported options: gaussian (default), binomial, poisson, gamma and tweedie.", "gaussian",
+               TC.toString),
+    "link": ("The name of link function which provides the relationship between the linear predictor and the "
+             "mean of the distribution function. Supported options: identity, log, inverse, logit, probit, "
+             "cloglog and sqrt.", NO_DEFAULT, TC.toString),
+    "variancePower": ("The power in the variance function of the Tweedie distribution which characterizes the "
+                      "relationship between the variance and mean of the distribution. Only applicable for the "
+                      "Tweedie family. Supported values: 0 and [1, Inf).", 0.0, TC.toFloat),
+    "linkPower": ("The index in the power link function. Only applicable to the Tweedie family.", NO_DEFAULT,
+                  TC.toFloat),
+    "fitIntercept": ("whether to fit an intercept term", True, TC.toBoolean),
+    "maxIter": ("max number of iterations (>= 0)", 25, TC.toInt),
+    "tol": ("the convergence tolerance for iterative algorithms (>= 0)", 1e-6, TC.toFloat),
+    "regParam": ("regularization parameter (>= 0)", 0.0, TC.toFloat),
+    "weightCol": ("weight column name", None, TC.toString),
+    "offsetCol": ("The offset column name. If this is not set or empty, we treat all instance offsets as 0.0",
+                  None, TC.toString),
+    "linkPredictionCol": ("link prediction (linear predictor) column name", None, TC.toString),
+    "solver": ("The solver algorithm for optimization. Supported options: irls.", "irls", TC.toString),
+    "aggregationDepth": ("suggested depth for treeAggregate (>= 2)", 2, TC.toInt),
+})
+
+
+def _glm_family_link(p):
+    """(family, link, variancePower, linkPower) of an estimator / model as the K22 op names them.  Tweedie with
+    variancePower 0 / 1 / 2 is the gaussian / poisson / gamma family and its power link 0 / 1 / -1 / 0.5 the
+    log / identity / inverse / sqrt link, as in Spark."""
+    family = p.getFamily().lower()
+    if p.getSolver().lower() != "irls":
+        raise IllegalArgumentException(f"GeneralizedLinearRegression solver must be irls, got {p.getSolver()}")
+    if family == "tweedie":
+        vp = float(p.getVariancePower())
+        if not (vp == 0.0 or vp >= 1.0):
+            raise IllegalArgumentException(
+                f"GeneralizedLinearRegression variancePower must be 0 or in [1, Inf), got {vp}")
+        lp = float(p.getLinkPower()) if p.isDefined("linkPower") else 1.0 - vp
+        return _GLM_POWER_FAMILIES.get(vp, "tweedie"), _GLM_POWER_LINKS.get(lp, "power"), vp, lp
+    if family not in _GLM_LINKS:
+        raise IllegalArgumentException(
+            f"GeneralizedLinearRegression family must be one of gaussian, binomial, poisson, gamma, tweedie, "
+            f"got {p.getFamily()}")
+    canonical, allowed = _GLM_LINKS[family]
+    link = p.getLink().lower() if p.isDefined("link") else canonical
+    if link not in allowed:
+        raise IllegalArgumentException(
+            f"Generalized Linear Regression with {family} family does not support {link} link function.")
+    return family, link, 0.0, 0.0
+
+
+def _glm_local(dataset, fc, lc, wc, oc):
+    """This rank's (X, y, w, offset): X fp32, or fp64 for course-sized Double vectors; the rest fp64 or None.
+    It is util.local_xyw(..., keep_f64=True) with one more column: the offset has to pass through the same
+    null-label filter as the weights, and local_xyw returns (X, y, w) only.  Keep the two in step."""
+    require_vector(dataset, fc)
+    from .util import feature_dtype, require_numeric
+    cols = [fc] + [c for c in (lc, wc, oc) if c]
+    for c in cols[1:]:
+        require_numeric(dataset, c)
+    b = local_batch(dataset, cols)
+    X = b.columns[fc].values
+    want = feature_dtype(X)
+    X = X if X.dtype == want else X.to(want)
+    y = b.columns[lc].values.to(torch.float64) if lc else None
+    w = b.columns[wc].values.to(torch.float64) if wc else None
+    off = b.columns[oc].values.to(torch.float64) if oc else None
+    keep = b.columns[lc].valid if lc else None
+    if keep is not None and not bool(keep.all()):
+        X, y = X[keep], y[keep]
+        w = None if w is None else w[keep]
+        off = None if off is None else off[keep]
+    return X, y, w, off
+
+
+def _glm_check_labels(family, vp, y, comm):
+    """Labels outside the family's domain, from one min / max pass."""
+    mm = torch.stack([y.min(), -y.max()]) if y.numel() else \
+        torch.full((2,), float("inf"), dtype=torch.float64, device=y.device)
+    comm.all_reduce(mm, "min")
+    lo, hi = float(mm[0]), -float(mm[1])
+    if lo > hi:
+        return
+    if family == "binomial" and (lo < 0.0 or hi > 1.0):
+        raise IllegalArgumentException(f"The binomial family requires labels in [0, 1], found [{lo}, {hi}]")
+    if (family == "poisson" or (family == "tweedie" and vp < 2.0)) and lo < 0.0:
+        raise IllegalArgumentException(f"The {family} family requires labels >= 0, found {lo}")
+    if (family == "gamma" or (family == "tweedie" and vp >= 2.0)) and lo <= 0.0:
+        raise IllegalArgumentException(f"The {family} family requires labels > 0, found {lo}")
+
+
+class GeneralizedLinearRegressionSummary:
+    """Fit statistics of a GLM on a dataset (``model.evaluate``), from small fp64 passes over (y, mu, w)."""
+
+    def __init__(self, predictions, model, data, comm, stats=None):
+        self.predictions = predictions
+        self.predictionCol = model.getPredictionCol()
+        self._model = model
+        self._X, self._y, self._w, self._off = data
+        self._comm = comm
+        self._fl = _glm_family_link(model)
+        self._stats = stats          # [deviance, sum w, sum w y] of the fit's final EVAL step, when there was one
+        self._cache = {}
+
+    # ------------------------------------------------------------ pieces
+    def _rows(self):
+        """(y, w, offset, eta, mu) of this rank's rows, fp64, computed once."""
+        if "rows" not in self._cache:
+            fam, link, _, lp = self._fl
+            m = self._model
+            y = self._y
+            w = torch.ones_like(y) if self._w is None else self._w
+            off = torch.zeros_like(y) if self._off is None else self._off
+            eta = off + m._intercept + K.matvec64(self._X, torch.tensor(m._coef, dtype=torch.float64))
+            mu = K.glm_clamp(fam, K.glm_unlink(link, eta, lp))
+            self._cache["rows"] = (y, w, off, eta, mu)
+            self._X = None
+        return self._cache["rows"]
+
+    def _sum(self, *ts):
+        acc = torch.stack([t.sum() for t in ts]).double()
+        self._comm.all_reduce(acc)
+        return [float(v) for v in acc.cpu()]
+
+    def _basic(self):
+        """[deviance, sum w, sum w y]."""
+        if self._stats is None:
+            fam, _, vp, _ = self._fl
+            y, w, _, _, mu = self._rows()
+            self._stats = self._sum(w * K.glm_unit_deviance(fam, y, mu, vp), w, w * y)
+        return self._stats
+
+    # ------------------------------------------------------------ fields
+    @property
+    def numInstances(self):
+        if "n" not in self._cache:
+            self._cache["n"] = int(self._comm.all_reduce_scalar(float(self._y.numel())))
+        return self._cache["n"]
+
+    @property
+    def rank(self):
+        return self._model.numFeatures + (1 if self._model.getFitIntercept() else 0)
+
+    @property
+    def degreesOfFreedom(self):
+        return self.numInstances - self.rank
+
+    @property
+    def residualDegreeOfFreedom(self):
+        return self.degreesOfFreedom
+
+    @property
+    def residualDegreeOfFreedomNull(self):
+        return self.numInstances - (1 if self._model.getFitIntercept() else 0)
+
+    @property
+    def deviance(self):
+        return self._basic()[0]
+
+    @property
+    def nullDeviance(self):
+        if "null" not in self._cache:
+            fam, link, vp, lp = self._fl
+            y, w, off, _, _ = self._rows()
+            m = self._model
+            one = torch.ones(1, dtype=torch.float64, device=y.device)
+            if not m.getFitIntercept():
+                b = 0.0
+            elif self._off is None:
+                _, sw, swy = self._basic()
+                b = float(K.glm_link(link, one * (swy / sw), lp)[0])
+            else:
+                # intercept-only IRLS with the offset, on the host formulation's row terms
+                b, mode = 0.0, K.GLM_INIT
+                for _ in range(max(m.getMaxIter(), 1) + 1):
+                    _, _, W, z, _ = K.glm_row_terms(y, w, off, b * one, fam, link, vp, lp, mode)
+                    swz, sw = self._sum(W * z, W)
+                    nb = swz / sw
+                    done = mode != K.GLM_INIT and abs(nb - b) < m.getTol()
+                    b, mode = nb, K.GLM_STEP
+                    if done:
+                        break
+            mu0 = K.glm_clamp(fam, K.glm_unlink(link, off + b, lp))
+            self._cache["null"] = self._sum(w * K.glm_unit_deviance(fam, y, mu0, vp))[0]
+        return self._cache["null"]
+
+    def _pearson(self):
+        fam, _, vp, _ = self._fl
+        y, w, _, _, mu = self._rows()
+        return (y - mu) * torch.sqrt(w) / torch.sqrt(K.glm_variance(fam, mu, vp))
+
+    @property
+    def dispersion(self):
+        if "disp" not in self._cache:
+            if self._fl[0] in ("binomial", "poisson"):
+                self._cache["disp"] = 1.0
+            else:
+                r = self._pearson()
+                self._cache["disp"] = self._sum(r * r)[0] / self.degreesOfFreedom
+        return self._cache["disp"]
+
+    @property
+    def aic(self):
+        if "aic" not in self._cache:
+            fam = self._fl[0]
+            y, w, _, _, mu = self._rows()
+            dev, sw, _ = self._basic()
+            n = self.numInstances
+            if fam == "gaussian":
+                ll = n * (math.log(dev / n * 2.0 * math.pi) + 1.0) + 2.0 - self._sum(torch.log(w))[0]
+            elif fam == "binomial":
+                nn = torch.round(w)
+                k = torch.round(y * w)
+                lp = (torch.lgamma(nn + 1) - torch.lgamma(k + 1) - torch.lgamma(nn - k + 1)
+                      + torch.xlogy(k, mu) + torch.xlogy(nn - k, 1.0 - mu))
+                ll = -2.0 * self._sum(torch.where(nn == 0, torch.zeros_like(lp), lp))[0]
+            elif fam == "poisson":
+                ll = -2.0 * self._sum(w * (torch.xlogy(y, mu) - mu - torch.lgamma(y + 1)))[0]
+            elif fam == "gamma":
+                disp = dev / sw
+                a, scale = 1.0 / disp, mu * disp
+                lp = (a - 1.0) * torch.log(y) - y / scale - a * torch.log(scale) - math.lgamma(a)
+                ll = -2.0 * self._sum(w * lp)[0] + 2.0
+            else:
+                raise RuntimeError("No AIC available for the tweedie family")
+            self._cache["aic"] = ll + 2.0 * self.rank
+        return self._cache["aic"]
+
+    def residuals(self, residualsType="deviance"):
+        fam, link, vp, lp = self._fl
+        y, w, _, _, mu = self._rows()
+        if residualsType == "deviance":
+            r = torch.sign(y - mu) * torch.sqrt((w * K.glm_unit_deviance(fam, y, mu, vp)).clamp_min(0.0))
+        elif residualsType == "pearson":
+            r = self._pearson()
+        elif residualsType == "working":
+            r = (y - mu) * K.glm_dlink(link, mu, lp)
+        elif residualsType == "response":
+            r = y - mu
+        else:
+            raise IllegalArgumentException(
+                f"The residuals type {residualsType} is not supported by Generalized Linear Regression.")
+        return self.predictions._session.createDataFrameFromLocalTensors({residualsType + "Residuals": r})
+
+
+class GeneralizedLinearRegressionTrainingSummary(GeneralizedLinearRegressionSummary):
+    def __init__(self, predictions, model, data, comm, stats, numIterations, solver, cov=None):
+        super().__init__(predictions, model, data, comm, stats)
+        self.numIterations = numIterations
+        self.solver = solver
+        self._cov = cov   # diag((X^T W X)^-1) of the last weighted least squares, intercept last; None: regParam > 0
+
+    @property
+    def coefficientStandardErrors(self):
+        if self._cov is None:
+            raise RuntimeError("No Std. Error of coefficients available for this GeneralizedLinearRegressionModel")
+        return [math.sqrt(max(self.dispersion * v, 0.0)) for v in self._cov]
+
+    @property
+    def tValues(self):
+        m = self._model
+        vals = list(m._coef) + ([m._intercept] if m.getFitIntercept() else [])
+        return [v / s if s > 0 else float("nan") for v, s in zip(vals, self.coefficientStandardErrors)]
+
+    @property
+    def pValues(self):
+        from scipy import stats
+        if self._fl[0] in ("binomial", "poisson"):
+            return [float(2.0 * stats.norm.sf(abs(t))) for t in self.tValues]
+        return [float(2.0 * stats.t.sf(abs(t), self.degreesOfFreedom)) for t in self.tValues]
+
+
+class GeneralizedLinearRegression(Estimator):
+    """IRLS, one fused pass over the features per iteration (K22 ``glm_step``): the step's (d+2)^2 weighted Gram and
+    its scalars are all-reduced in one buffer and the weighted least squares is solved on the host by the solver
+    LinearRegression's normal-equation path uses (standardised, L2 ``regParam``)."""
+    _params = _GLM_PARAMS
+
+    def __init__(self, labelCol=None, featuresCol=None, predictionCol=None, family=None, link=None,
+                 fitIntercept=None, maxIter=None, tol=None, regParam=None, weightCol=None, solver=None,
+                 linkPredictionCol=None, variancePower=None, linkPower=None, offsetCol=None, aggregationDepth=None):
+        super().__init__()
+        keyword_init(self, {k: v for k, v in locals().items() if k not in ("self", "__class__")})
+
+    def _fit(self, dataset):
+        fam, link, vp, lp = _glm_family_link(self)
+        fc, lc = self.getFeaturesCol(), self.getLabelCol()
+        wc, oc = self.getWeightCol() or None, self.getOffsetCol() or None
+        X, y, w, off = _glm_local(dataset, fc, lc, wc, oc)
+        comm = dataset._session.comm
+        d = X.shape[1]
+        dev = X.device
+        _glm_check_labels(fam, vp, y, comm)
+        fit_int = self.getFitIntercept()
+        shift = shift_h = None
+        zshift = 0.0
+        one = torch.ones(1, dtype=torch.float64)
+        if fit_int:
+            # the features' shift and a first centre of the working response, from the leading rows: they only
+            # condition the fp32 Gram, the solve un-shifts exactly
+            sh = _lr_shift(X[:4096], y[:4096], comm, d).cpu()
+            shift = sh[:d].float().to(dev)
+            shift_h = sh[:d].float().double().numpy()
+            z0 = K.glm_link(link, K.glm_clamp(fam, K.glm_init_mu(fam, one * float(sh[d]), one)), lp)
+            zshift = float(z0[0]) if bool(torch.isfinite(z0[0])) else 0.0
+        wls = LinearRegression(regParam=self.getRegParam(), elasticNetParam=0.0, fitIntercept=fit_int,
+                               standardization=True)
+        nG = (d + 2) * (d + 2)
+
+        def step(coef, b, zs, mode, it):
+            beta = None if coef is None else torch.tensor(coef, dtype=torch.float64, device=dev)
+            G, st = K.glm_step(X, y, w, off, beta, b, shift, zs, fam, link, vp, lp, mode)
+            buf = torch.cat([G.reshape(-1), st])
+            comm.all_reduce(buf)
+            host = buf.cpu().numpy()
+            if host[nG + 3] > 0:
+                raise RuntimeError(
+                    f"GeneralizedLinearRegression (family {fam}, link {link}): {int(host[nG + 3])} rows have a "
+                    f"non-finite mean, working weight or working response at iteration {it}; the fit diverged")
+            return host[:nG].reshape(d + 2, d + 2), host[nG:]
+
+        def solve(G, zs):
+            coef, b = wls._solve(G, d, shift_h, float(np.float32(zs)) if fit_int else 0.0)[:2]
+            return np.asarray(coef, np.float64), float(b)
+
+        def centre(G, zs):
+            # the weighted mean of the working response: the next step's zshift
+            return float(np.float32(zs)) + G[d + 1, d] / G[d, d] if fit_int and G[d, d] > 0 else 0.0
+
+        zs = zshift
+        G, _ = step(None, 0.0, zs, K.GLM_INIT, 0)
+        coef, b = solve(G, zs)
+        iters = 0
+        if not (fam == "gaussian" and link == "identity"):
+            tol, max_iter = self.getTol(), self.getMaxIter()
+            while iters < max_iter:
+                zs = centre(G, zs)
+                G, _ = step(coef, b, zs, K.GLM_STEP, iters + 1)
+                ncoef, nb = solve(G, zs)
+                iters += 1
+                delta = max(float(np.max(np.abs(ncoef - coef))) if d else 0.0, abs(nb - b))
+                coef, b = ncoef, nb
+                if delta < tol:
+                    break
+        _, st = step(coef, b, 0.0, K.GLM_EVAL, iters)
+        model = GeneralizedLinearRegressionModel(coef, b)
+        model._post_fit(self)
+        cov = self._cov_diag(G, d, shift_h, fit_int) if self.getRegParam() == 0.0 else None
+        model.summary = GeneralizedLinearRegressionTrainingSummary(
+            model.transform(dataset), model, (X, y, w, off), comm, [float(v) for v in st[:3]], iters,
+            self.getSolver(), cov)
+        return model
+
+    @staticmethod
+    def _cov_diag(G, d, shift, fit_int):
+        """diag((X^T W X)^-1) in uncentred coordinates (intercept last) from the shifted Gram: [x | 1] =
+        [x - s | 1] T with T = [[I, 0], [s^T, 1]], so X^T W X = T^T G T."""
+        k = d + 1 if fit_int else d
+        M = np.array(G[:k, :k], dtype=np.float64)
+        if fit_int and shift is not None:
+            Tm = np.eye(k)
+            Tm[d, :d] = shift
+            M = Tm.T @ M @ Tm
+        try:
+            return list(np.diag(np.linalg.inv(M)))
+        except np.linalg.LinAlgError:
+            return None
+
+
+class GeneralizedLinearRegressionModel(Model):
+    _params = _GLM_PARAMS
+
+    def __init__(self, coefficients=None, intercept=0.0):
+        super().__init__()
+        self._coef = np.asarray(coefficients if coefficients is not None else [], dtype=np.float64)
+        self._intercept = float(intercept)
+        self.summary = None
+
+    @property
+    def coefficients(self):
+        return DenseVector(self._coef)
+
+    @property
+    def intercept(self):
+        return self._intercept
+
+    @property
+    def numFeatures(self):
+        return len(self._coef)
+
+    @property
+    def hasSummary(self):
+        return self.summary is not None
+
+    def predict(self, features):
+        fam, link, _, lp = _glm_family_link(self)
+        x = features.toArray() if hasattr(features, "toArray") else np.asarray(features)
+        eta = torch.tensor([float(x @ self._coef + self._intercept)], dtype=torch.float64)
+        return float(K.glm_clamp(fam, K.glm_unlink(link, eta, lp))[0])
+
+    def _transform(self, dataset):
+        fam, link, _, lp = _glm_family_link(self)
+        fc, pc = self.getFeaturesCol(), self.getPredictionCol()
+        lpc, oc = self.getLinkPredictionCol() or None, self.getOffsetCol() or None
+        require_vector(dataset, fc)
+        coef = torch.tensor(self._coef, dtype=torch.float64)
+        icpt = self._intercept
+
+        def fn(b, ctx):
+            X = b.columns[fc].values
+            eta = K.matvec64(X, coef) + icpt
+            if oc:
+                eta = eta + b.columns[oc].values.to(torch.float64)
+            mu = K.glm_clamp(fam, K.glm_unlink(link, eta, lp))
+            out = b.with_column(pc, ColumnData(mu, T.DoubleType(), b.columns[fc].valid))
+            if lpc:
+                out = out.with_column(lpc, ColumnData(eta, T.DoubleType(), b.columns[fc].valid))
+            return out
+        return dataset._new(MapPlan(dataset._plan, f"GeneralizedLinearRegressionModel -> {pc}", fn))
+
+    def evaluate(self, dataset):
+        data = _glm_local(dataset, self.getFeaturesCol(), self.getLabelCol(), self.getWeightCol() or None,
+                          self.getOffsetCol() or None)
+        return GeneralizedLinearRegressionSummary(self.transform(dataset), self, data, dataset._session.comm)
+
+    def _save_state(self):
+        return {"intercept": self._intercept}, {"coefficients": torch.tensor(self._coef)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._coef = tensors["coefficients"].numpy()
+        self._intercept = float(extra["intercept"])
+        self.summary = None
+
+    def __repr__(self):
+        return f"GeneralizedLinearRegressionModel: uid={self.uid}, family={self.getFamily()}, " \
+               f"numFeatures={self.numFeatures}"

@@ -226,6 +226,11 @@ _SIGS = {
                         c_void_p], c_int),
     "cdna_logistic_grad": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                             c_void_p, c_int, c_void_p], c_int),
+    "cdna_glm_step_blocks": ([c_int64], c_int),
+    "cdna_glm_step_workspace": ([c_int64, c_int], c_int64),
+    "cdna_glm_step": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                       c_float, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                       c_void_p], c_int),
 }
 
 

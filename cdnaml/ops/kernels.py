@@ -1585,6 +1585,233 @@ def logistic_grad(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, b: float,
     return g, loss
 
 
+# -------------------------------------------------------------------- K22
+GLM_FAMILY = {"gaussian": 0, "binomial": 1, "poisson": 2, "gamma": 3, "tweedie": 4}
+GLM_LINK = {"identity": 0, "log": 1, "inverse": 2, "logit": 3, "probit": 4, "cloglog": 5, "sqrt": 6, "power": 7}
+GLM_STEP, GLM_INIT, GLM_EVAL = 0, 1, 2
+GLM_EPS = 1e-16      # Spark's clamp of the mean (binomial into [eps, 1 - eps], poisson / gamma / tweedie >= eps)
+GLM_MAX_D = 126      # the fused kernel's range: d + 2 <= 128
+_SQRT_2PI = 2.5066282746310002
+
+
+def glm_link(link: str, mu: torch.Tensor, lp: float = 0.0) -> torch.Tensor:
+    """eta = g(mu) (fp64 tensors; ``lp`` is the exponent of the "power" link)."""
+    if link == "identity":
+        return mu
+    if link == "log":
+        return torch.log(mu)
+    if link == "inverse":
+        return 1.0 / mu
+    if link == "logit":
+        return torch.log(mu / (1.0 - mu))
+    if link == "probit":
+        return torch.special.ndtri(mu)
+    if link == "cloglog":
+        return torch.log(-torch.log(1.0 - mu))
+    if link == "sqrt":
+        return torch.sqrt(mu)
+    return torch.pow(mu, lp)
+
+
+def glm_unlink(link: str, eta: torch.Tensor, lp: float = 0.0) -> torch.Tensor:
+    """mu = g^-1(eta), before the family's clamp."""
+    if link == "identity":
+        return eta
+    if link == "log":
+        return torch.exp(eta)
+    if link == "inverse":
+        return 1.0 / eta
+    if link == "logit":
+        return 1.0 / (1.0 + torch.exp(-eta))
+    if link == "probit":
+        return torch.special.ndtr(eta)
+    if link == "cloglog":
+        return 1.0 - torch.exp(-torch.exp(eta))
+    if link == "sqrt":
+        return eta * eta
+    return torch.pow(eta, 1.0 / lp)
+
+
+def glm_dlink(link: str, mu: torch.Tensor, lp: float = 0.0) -> torch.Tensor:
+    """g'(mu)."""
+    if link == "identity":
+        return torch.ones_like(mu)
+    if link == "log":
+        return 1.0 / mu
+    if link == "inverse":
+        return -1.0 / (mu * mu)
+    if link == "logit":
+        return 1.0 / (mu * (1.0 - mu))
+    if link == "probit":
+        q = torch.special.ndtri(mu)
+        return _SQRT_2PI * torch.exp(0.5 * q * q)
+    if link == "cloglog":
+        return 1.0 / ((mu - 1.0) * torch.log(1.0 - mu))
+    if link == "sqrt":
+        return 0.5 / torch.sqrt(mu)
+    return lp * torch.pow(mu, lp - 1.0)
+
+
+def glm_clamp(family: str, mu: torch.Tensor) -> torch.Tensor:
+    # NaN stays NaN (torch.where, not clamp): the step counts such rows instead of hiding them
+    if family == "binomial":
+        mu = torch.where(mu < GLM_EPS, torch.full_like(mu, GLM_EPS), mu)
+        return torch.where(mu > 1.0 - GLM_EPS, torch.full_like(mu, 1.0 - GLM_EPS), mu)
+    if family == "gaussian":
+        return mu
+    return torch.where(mu < GLM_EPS, torch.full_like(mu, GLM_EPS), mu)
+
+
+def glm_variance(family: str, mu: torch.Tensor, vp: float = 0.0) -> torch.Tensor:
+    if family == "gaussian":
+        return torch.ones_like(mu)
+    if family == "binomial":
+        return mu * (1.0 - mu)
+    if family == "poisson":
+        return mu
+    if family == "gamma":
+        return mu * mu
+    return torch.pow(mu, vp)
+
+
+def _ylogy(y: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+    return torch.where(y == 0, torch.zeros_like(y), y * torch.log(y / mu))
+
+
+def _tw_yp(y, mu, p: float):
+    return torch.log(y / mu) if p == 0.0 else (torch.pow(y, p) - torch.pow(mu, p)) / p
+
+
+def glm_unit_deviance(family: str, y: torch.Tensor, mu: torch.Tensor, vp: float = 0.0) -> torch.Tensor:
+    """d(y, mu); a row's deviance is its weight times this."""
+    if family == "gaussian":
+        return (y - mu) * (y - mu)
+    if family == "binomial":
+        return 2.0 * (_ylogy(y, mu) + _ylogy(1.0 - y, 1.0 - mu))
+    if family == "poisson":
+        return 2.0 * (_ylogy(y, mu) - (y - mu))
+    if family == "gamma":
+        return -2.0 * (torch.log(y / mu) - (y - mu) / mu)
+    y1 = y.clamp_min(0.1) if 1.0 <= vp < 2.0 else y
+    return 2.0 * (y * _tw_yp(y1, mu, 1.0 - vp) - _tw_yp(y, mu, 2.0 - vp))
+
+
+def glm_init_mu(family: str, y: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """The family's starting mean (R / Spark)."""
+    if family == "binomial":
+        return (w * y + 0.5) / (w + 1.0)
+    if family in ("poisson", "tweedie"):
+        return y.clamp_min(0.1)
+    return y
+
+
+def matvec64(X: torch.Tensor, beta: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
+    """X @ beta in fp64 without an fp64 copy of a large fp32 X."""
+    b = beta.double().to(X.device)
+    if X.dtype == torch.float64 or X.shape[0] <= chunk:
+        return X.double() @ b
+    return torch.cat([X[i:i + chunk].double() @ b for i in range(0, X.shape[0], chunk)])
+
+
+def glm_row_terms(y, w, offset, lin, family: str, link: str, vp: float, lp: float, mode: int):
+    """(eta, mu, W, z, finite) of every row, fp64: ``lin`` is b + x.beta (ignored in INIT mode)."""
+    if mode == GLM_INIT:
+        mu = glm_clamp(family, glm_init_mu(family, y, w))
+        eta = glm_link(link, mu, lp)
+    else:
+        eta = offset + lin
+        mu = glm_clamp(family, glm_unlink(link, eta, lp))
+    gp = glm_dlink(link, mu, lp)
+    W = w / (glm_variance(family, mu, vp) * gp * gp)
+    z = eta - offset + (y - mu) * gp
+    fin = torch.isfinite(mu) & torch.isfinite(W) & torch.isfinite(z)
+    return eta, mu, W, z, fin
+
+
+def glm_step(X: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], offset: Optional[torch.Tensor],
+             beta: Optional[torch.Tensor], intercept: float, shift: Optional[torch.Tensor], zshift: float,
+             family: str, link: str, var_power: float = 0.0, link_power: float = 0.0, mode: int = GLM_STEP):
+    """One IRLS pass of a generalized linear model (local sums): returns (G[d+2, d+2], stats[4]), both fp64.
+
+    Per row, in fp64: eta = offset + intercept + x.beta, mu = g^-1(eta) clamped as Spark's families clamp it,
+    gp = g'(mu), working weight W = w / (V(mu) gp^2), working response z = eta - offset + (y - mu) gp.
+    G is the Gram of sqrt(W) [x - shift | 1 | z - zshift] in K.gram's layout (sum W x~x~^T, sum W x~, sum W,
+    sum W x~ z~, sum W z~, sum W z~^2); stats = [sum w d(y, mu), sum w, sum w y, rows whose mu, W or z is not
+    finite].  Such rows are left out of G and of the sums: their augmented row is zeroed, so an inf / NaN feature
+    that makes eta non-finite does not reach G (in INIT mode the features do not enter eta, and a non-finite
+    feature goes into G as it is).  ``zshift`` is used as its fp32 rounding.
+    mode GLM_INIT: eta = g(mu0) with the family's starting mean from the label, beta unused.
+    mode GLM_EVAL: stats only, G is zeros.
+    family / link are names (GLM_FAMILY, GLM_LINK); "power" takes ``link_power``, "tweedie" ``var_power``.
+
+    fp32 X on a GPU with d + 2 <= 128 (any n >= 1, row stride and alignment) runs the fused K22 kernel: one
+    launch that reads X once, exact-fp32 MFMA Gram with the augmented row rounded to fp32, partial sums reduced
+    in a fixed order: two calls on the same input return the same bits.  Bit-identical reruns of G are part of
+    the contract inside this range only: past the cap G comes from K.gram's fp32 path, whose LDS float atomics
+    fold the waves in no fixed order.  Everything else takes the host formulation, the same formulas as torch
+    fp64 ops: fp64 X entirely in fp64; fp32 X past the cap on a GPU through a scaled copy and
+    K.gram(fp64=False).
+    """
+    n, d = X.shape
+    dev = X.device
+    fam_id, link_id = GLM_FAMILY[family], GLM_LINK[link]
+    zs = float(np.float32(zshift))
+    yd = y.double().contiguous()
+    wd = None if w is None else w.double().contiguous()
+    od = None if offset is None else offset.double().contiguous()
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    if _native(X) and X.dtype == torch.float32 and 1 <= d <= GLM_MAX_D and n >= 1:
+        X = X if X.stride(1) == 1 and X.stride(0) >= d else X.contiguous()
+        bd = None if beta is None else beta.double().to(dev).contiguous()
+        sh = None if shift is None else shift.float().to(dev).contiguous()
+        L = _lib.lib()
+        ws = torch.empty(max(L.cdna_glm_step_workspace(n, d), 1), dtype=torch.float32, device=dev)
+        sws = torch.empty(4 * L.cdna_glm_step_blocks(n), dtype=torch.float64, device=dev)
+        G = torch.zeros((d + 2, d + 2), dtype=torch.float64, device=dev)
+        stats = torch.zeros(4, dtype=torch.float64, device=dev)
+        _lib.check(L.cdna_glm_step(_ptr(X), n, d, X.stride(0), _ptr(yd), _ptr(wd), _ptr(od), _ptr(bd),
+                                   float(intercept), _ptr(sh), zs, fam_id, link_id, float(var_power),
+                                   float(link_power), int(mode), _ptr(G), _ptr(stats), _ptr(ws), _ptr(sws),
+                                   _stream(dev)), "cdna_glm_step")
+        return G, stats
+    # host formulation
+    ww = torch.ones_like(yd) if wd is None else wd
+    oo = torch.zeros_like(yd) if od is None else od
+    lin = None
+    if mode != GLM_INIT:
+        lin = float(intercept) + (matvec64(X, beta) if beta is not None else torch.zeros_like(yd))
+    _, mu, W, z, fin = glm_row_terms(yd, ww, oo, lin, family, link, var_power, link_power, mode)
+    zero = torch.zeros_like(yd)
+    wf = torch.where(fin, ww, zero)
+    stats = torch.stack([torch.where(fin, ww * glm_unit_deviance(family, yd, mu, var_power), zero).sum(),
+                         wf.sum(), (wf * yd).sum(), (~fin).sum().double()])
+    if mode == GLM_EVAL:
+        return torch.zeros((d + 2, d + 2), dtype=torch.float64, device=dev), stats
+    sw = torch.sqrt(torch.where(fin, W, zero))
+    zt = sw * (torch.where(fin, z, zero) - zs)
+    if X.dtype == torch.float32 and _native(X) and d + 3 <= 512:
+        # past the fused kernel's range: a sqrt(W)-scaled copy with sqrt(W) itself as an extra feature, then K1
+        sw32 = sw.float()[:, None]
+        Xw = torch.cat([(X - (shift.float().to(dev) if shift is not None else 0.0)) * sw32, sw32], 1)
+        Xw = torch.where(fin[:, None], Xw, torch.zeros_like(Xw))
+        G3 = gram(Xw, zt.float(), None, 0.0, fp64=False) if n else \
+            torch.zeros((d + 3, d + 3), dtype=torch.float64, device=dev)
+        keep = torch.tensor(list(range(d + 1)) + [d + 2], device=dev)
+        return G3[keep][:, keep].contiguous(), stats
+    A = torch.empty((n, d + 2), dtype=torch.float64, device=dev)
+    if X.dtype == torch.float64:
+        A[:, :d] = (X if shift is None else X - shift.double().to(dev)) * sw[:, None]
+    else:   # the kernel's arithmetic: x - shift and its scaling in fp32
+        A[:, :d] = (X if shift is None else X - shift.float().to(dev)) * sw.float()[:, None]
+    A[:, d] = sw
+    A[:, d + 1] = zt
+    A = torch.where(fin[:, None], A, torch.zeros_like(A))   # a left-out row is zeroed, not scaled by 0
+    if X.dtype == torch.float32:
+        A = A.float().double()   # the augmented row rounded to fp32, as the kernel feeds it to the MFMA
+    return A.T @ A, stats
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
