@@ -1518,7 +1518,9 @@ def score_hist(score: torch.Tensor, label: torch.Tensor, lo: float, hi: float, n
                                               _ptr(h), _stream(score.device)), "cdna_score_hist")
         return h
     scale = nb / (hi - lo) if hi > lo else 0.0
-    b = ((score - lo) * scale).floor().long().clamp(0, nb - 1)
+    # clamped before the conversion, as in the kernel: +inf -> the last bucket, -inf and NaN -> bucket 0
+    t = (score - lo) * scale
+    b = torch.where(t.isnan(), torch.zeros_like(t), t).clamp(0, nb - 1).long()
     pos = (label > 0.5).long()
     h = torch.zeros(nb * 2, dtype=torch.float64)
     h.index_add_(0, b * 2 + pos, torch.ones_like(score))

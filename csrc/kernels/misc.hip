@@ -255,8 +255,10 @@ __global__ __launch_bounds__(256) void score_hist_kernel(const double* __restric
                                                          double hi, int nb, double* __restrict__ hist) {
   const double scale = hi > lo ? (double)nb / (hi - lo) : 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    int b = (int)((score[i] - lo) * scale);
-    b = b < 0 ? 0 : (b >= nb ? nb - 1 : b);
+    // clamped in floating point, before the conversion (an out-of-range double -> int is not defined): +inf and
+    // every score >= hi land in the last bucket, -inf, every score < lo and NaN (neither compare holds) in bucket 0
+    const double t = (score[i] - lo) * scale;
+    const int b = t >= (double)nb ? nb - 1 : (t > 0.0 ? (int)t : 0);
     atomicAdd(&hist[b * 2 + (label[i] > 0.5 ? 1 : 0)], 1.0);
   }
 }
@@ -285,7 +287,10 @@ __global__ __launch_bounds__(256) void kmeans_kernel(const T* __restrict__ X, in
   double mycost = 0.0;
   for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
     const T* x = X + r * ldx;
-    T best = T(3.4e38);
+    // the minimum as torch.min takes it (the host path of K.kmeans_step): the lowest index among equal distances,
+    // centre 0 when every distance overflowed to +inf, and the first NaN distance wins and stays -- a row that
+    // cannot be placed makes the cost inf / NaN instead of adding a large finite number to it
+    T best = T(INFINITY);
     int bi = 0;
     for (int c = 0; c < k; ++c) {
       T dist = T(0);
@@ -293,7 +298,7 @@ __global__ __launch_bounds__(256) void kmeans_kernel(const T* __restrict__ X, in
         const T df = x[f] - sc[c * d + f];
         dist += df * df;
       }
-      if (dist < best) {
+      if (dist < best || (dist != dist && best == best)) {
         best = dist;
         bi = c;
       }

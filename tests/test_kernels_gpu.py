@@ -369,6 +369,8 @@ def test_kmeans_step(dev):
     assert torch.equal(a1, a2.cpu())
     assert torch.allclose(s1, s2.cpu(), rtol=1e-5, atol=1e-3)
     assert torch.allclose(c1, c2.cpu())
+    # both costs are fp64 sums of fp32 distances, each within (d + 2) eps of the exact one (d = 4)
+    assert abs(float(cost1) - float(cost2)) <= 2 * 6 * 2.0 ** -23 * float(cost1)
 
 
 def test_logistic_grad(dev):
