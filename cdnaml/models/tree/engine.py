@@ -56,6 +56,10 @@ NATIVE_SPLIT = True
 MSEG_REC = True
 # level 0 on seg10 rows: root records compacted inside the histogram kernel (no codes_compact pass)
 ROOT_HIST = True
+# the level-0 row partition inside the level-1 codes histogram (seg.hip RootMove): the LDS-bound kernel moves each
+# row's code itself instead of a partition7 pass in series ahead of it (4 GB of codes read and written, <= 10 GB
+# of bins words: ~2.7 ms of the headline step)
+ROOT_MOVE = True
 # regression forests (T > 1) deeper than 8 levels: the packed record levels down to 8, then node ids (as binary
 # classification); 0 = the node-id histograms from the root (round 3).  RF 20 trees depth 10 at 1e7 x 100:
 # 376 -> 88 ms per fit.  One tree keeps the permutation segment path (seg.hip, any depth): 14 ms at depth 12
@@ -391,12 +395,31 @@ class ForestTrainer:
             raise RuntimeError("device split decode differs from the host decode")
 
     # ------------------------------------------------------------ device-queued partition
+    def _root_move_ok(self, st: "_FitState", depth: int, mb: bool) -> bool:
+        """Level 0 of a forest on seg10 rows with numeric splits: its row partition is left to the level-1 codes
+        histogram (ROOT_MOVE; forests the partition7 pass serves, as that is the pass it replaces)."""
+        data = self.data
+        return (ROOT_MOVE and depth == 0 and self.device.type == "cuda" and data.bins_s10 is not None and
+                self._root_rows() is data.bins_s10 and st.use_mseg and st.rec_ok and not st.margin_ok and
+                not data.categorical and not mb and st.node is None and
+                K.PARTITION7 and K.PARTITION7_MIN_T <= st.T <= 64)
+
+    def _late_partition(self, st: "_FitState", depth: int) -> None:
+        """The level-0 row partition that ``_device_partition`` left to the level-1 histogram, for a level 1 that
+        cannot take it (a root that did not split, no codes histogram): nothing has read the codes since."""
+        dec, tf_d = st.late_move
+        st.late_move = None
+        with _tr.span("tree.partition", depth=depth - 1):
+            K.partition_codes(self.data.bins, st.codes, tf_d, dec["tfirst_next"], dec["split_feat"],
+                              dec["split_bin"], dec["cat_off"], dec["masks"].reshape(-1), dec["child"])
+
     def _device_partition(self, so, tot, a_tree, tfirst, T, depth, mb, codes, margin=None, catm=None, node=None,
-                          pre=None):
+                          pre=None, late=None):
         """Partition tables decoded on the device from the level's K6 decisions and the row partition queued right
         behind them (the GPU partitions while the decisions travel to the host; the host repeats the decode to
         build the forest and the next level, checked against the device's in the checked build).  -> the decode
-        tables."""
+        tables.  late (a _FitState, ``_root_move_ok``): the partition is not queued; the tables wait on the state
+        for the next level's histogram."""
         p, data, dev = self.p, self.data, self.device
         # (``pre``: the two tables uploaded at the level start with the level's other small tables)
         a_tree_d, tf_d = pre if pre is not None else \
@@ -405,6 +428,9 @@ class ForestTrainer:
                              depth < p.max_depth, depth + 1 >= p.max_depth, missing_bin=mb,
                              leaf_values=(p.impurity, p.reg_lambda) if margin is not None else None,
                              catm=catm, nthr=self._nthr_dev(dev) if catm is not None else None)
+        if late is not None:
+            late.late_move = (dec, tf_d)
+            return dec
         with _tr.span("tree.partition", depth=depth):
             if node is not None:
                 # levels below the u16 codes: the node-id partition from the same device tables (child = the
@@ -664,6 +690,7 @@ class ForestTrainer:
         st.prev_hist = None  # [A_prev, d, B, k] histograms of last level's split nodes
         st.rs_on = False     # this pass reduce-scatters its level histograms by feature (RS_MIN_BYTES)
         st.root_ids = [None] * T
+        st.late_move = None  # (decode tables, tfirst): level 0's row partition, left to level 1 (ROOT_MOVE)
         st.deep_rec = False  # set at the switch to node ids (deep_switch)
         st.wdeep = None
         st.node_count = st.forest.num_nodes
@@ -855,6 +882,15 @@ class ForestTrainer:
                 st.lazy_codes.materialize()
             st.lazy_codes.mark_drawn()
             st.lazy_codes = None
+        move = None
+        if st.late_move is not None:
+            # level 0's row partition was left to this level: the codes histogram moves the rows itself when every
+            # tree has its one built node here (every root split), else the partition runs now, late
+            if root_ok and S == T and root_rows is data.bins_s10:
+                move = (st.late_move[0], data.bins, True)  # (numeric splits: _root_move_ok)
+                st.late_move = None
+            else:
+                self._late_partition(st, depth)
         if root_ok:
             sl_node = build_ids - tfirst.numpy()[slot_tree]  # the slot's local node in its tree's codes
             # one launch for every slot, then the level's one all-reduce: these levels hold one node per
@@ -863,7 +899,7 @@ class ForestTrainer:
             lv.Hb = K.seg_hist_codes(root_rows, d, B, st.codes, stats_rows["v1"], st.mseg_scales[1], wmax,
                                      slot_tree, sl_node, 0, S,
                                      torch.zeros((S, d, B, K.hist_cols(st.cls3)), dtype=torch.int64, device=dev),
-                                     draw=draw, cls3=st.cls3)
+                                     draw=draw, cls3=st.cls3, move=move)
             lv.hist_raw_scale = st.mseg_raw
         elif st.use_mseg and (depth >= 1 or MSEG_L0):
             # gather the rows of the built nodes into slot segments, then segment histograms of packed
@@ -998,7 +1034,8 @@ class ForestTrainer:
                 # and the next level's layout (the same decode on the host, checked in the checked build)
                 lv.dec = self._device_partition(so, tot, st.a_tree, lv.tfirst, T, depth, mb, st.codes,
                                                 margin=st.margin if st.margin_ok else None,
-                                                node=st.node if deep_ids else None, pre=pre)
+                                                node=st.node if deep_ids else None, pre=pre,
+                                                late=st if self._root_move_ok(st, depth, mb) else None)
             # so [A, 8] = gain, feature, bin, left (2), right (2), missing-goes-right: copied to the host as is
             # (plus the node totals at level 0), no per-column device ops
             sw = so.shape[1]
@@ -1045,7 +1082,8 @@ class ForestTrainer:
                     tot_d = tot
                 lv.dec = self._device_partition(so_d, tot_d, st.a_tree, lv.tfirst, T, depth, False, st.codes,
                                                 catm=cm if self.data.categorical else None,
-                                                node=st.node if deep_ids else None, pre=pre)
+                                                node=st.node if deep_ids else None, pre=pre,
+                                                late=st if self._root_move_ok(st, depth, False) else None)
                 st.flush()
                 host_ev.synchronize()
                 host = host_p.numpy()

@@ -119,6 +119,9 @@ _SIGS = {
                                  c_void_p, c_int, c_void_p, c_int, c_void_p], c_int),
     "cdna_seg_hist_root": ([c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p,
                             c_int, c_void_p, c_int, c_uint64, c_uint64, c_double, c_int, c_void_p], c_int),
+    "cdna_seg_hist_root_move": ([c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,
+                                 c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_void_p], c_int),
     "cdna_poisson_max_draw": ([c_double], c_int),
     "cdna_seg_partition": ([c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

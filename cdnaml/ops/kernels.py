@@ -2132,7 +2132,8 @@ def _num_cus(dev) -> int:
 
 def seg_hist_codes(bins_s10: torch.Tensor, d: int, B: int, codes: torch.Tensor, v1: torch.Tensor, qs1: float,
                    wmax: int, slot_tree: np.ndarray, slot_node: np.ndarray, s0: int, s1: int,
-                   out: torch.Tensor, draw: Optional[tuple] = None, cls3: bool = False) -> torch.Tensor:
+                   out: torch.Tensor, draw: Optional[tuple] = None, cls3: bool = False,
+                   move: Optional[tuple] = None) -> torch.Tensor:
     """Record histograms of slots [s0, s1) straight from the row codes (GPU, seg10 rows), for levels with at most
     one built node per tree: slot s is local node ``slot_node[s]`` of tree ``slot_tree[s]`` (level 0: every root,
     node 0).  Adds the exact int64 sums (count, sum w * q) into ``out`` [s1 - s0, d, B, 2] (zeroed by the caller)
@@ -2141,7 +2142,12 @@ def seg_hist_codes(bins_s10: torch.Tensor, d: int, B: int, codes: torch.Tensor, 
 
     draw (level 0 of a bootstrapped forest, B <= 40): ``(seed, row offset, rate)`` -- the kernel draws every row's
     Poisson weight itself and WRITES ``codes`` (the lazy :class:`BootstrapCodes`); ``wmax`` must then be the draws'
-    static bound (``poisson_max_draw``)."""
+    static bound (``poisson_max_draw``).
+
+    move (level 1, B <= 40, slots [0, T): one per tree): ``(dec, bins[, numeric])`` -- ``codes`` still hold level 0
+    (the row partition was not run): the kernel moves them to level 1 in place, as ``partition_codes`` with
+    ``split_decode``'s level-0 tables ``dec`` and the column-major ``bins`` [G, n, 8] would have, and builds the
+    histograms of the moved codes.  Numeric splits only (``numeric``: the caller vouches, no device read)."""
     T, n = codes.shape
     wide = 80 < B <= 256
     # B <= 40: seg10 rows, six-items-per-wave kernel; 80 < B <= 256 (boosting): standard row-major rows, lane4
@@ -2153,6 +2159,18 @@ def seg_hist_codes(bins_s10: torch.Tensor, d: int, B: int, codes: torch.Tensor, 
     sn = np.asarray(slot_node, dtype=np.int64)
     assert len(st) == len(sn) and np.all((st >= 0) & (st < T)) and np.all((sn >= 0) & (sn < 0xFF))
     assert len(np.unique(st[s0:s1])) == s1 - s0  # one built node per tree
+    if move is not None:
+        dec, bins_cm = move[0], move[1]
+        G = bins_cm.shape[0]
+        tabs = [dec[k].to(device=codes.device, dtype=torch.int32).contiguous()
+                for k in ("split_feat", "split_bin", "cat_off", "child", "tfirst_next")]
+        assert draw is None and not wide and d <= 100 and B <= 40, "the fused move runs on seg10 rows, drawn codes"
+        assert s0 == 0 and s1 - s0 == T, "the fused move needs one slot per tree (else a tree's codes stay unmoved)"
+        assert _native(bins_cm) and bins_cm.dtype == torch.uint8 and bins_cm.is_contiguous() and \
+            bins_cm.shape == (G, n, 8) and G * 8 >= d
+        assert [t.numel() for t in tabs] == [T, T, T, 2 * T, T], "level-0 tables: one active node per tree"
+        # (the trainer knows from the host that its splits are numeric; any other caller pays one device read)
+        assert (len(move) > 2 and move[2]) or not bool((tabs[2] >= 0).any()), "categorical / bin-set root split"
     if n == 0 or s1 <= s0:
         return out
     wm = int(max(1, min(255, wmax)))
@@ -2173,6 +2191,13 @@ def seg_hist_codes(bins_s10: torch.Tensor, d: int, B: int, codes: torch.Tensor, 
                    "cdna_seg_hist_root_wide")
         return out
     wt, si = upload(codes.device, work.reshape(-1), sinfo)
+    if move is not None:
+        _lib.check(_lib.lib().cdna_seg_hist_root_move(_ptr(bins_s10), n, d, B, _ptr(codes), _ptr(v1c), float(qs1),
+                                                      _ptr(wt), len(work), _ptr(si), s0, _ptr(out), _ptr(bins_cm), G,
+                                                      T, *[_ptr(t) for t in tabs], int(cls3),
+                                                      _stream(codes.device)),
+                   "cdna_seg_hist_root_move")
+        return out
     if draw is not None:
         assert np.array_equal(np.sort(st[s0:s1]), np.arange(T)) and not np.any(sn[s0:s1]), "draws need every root"
     seed, off, rate = draw if draw is not None else (0, 0, 1.0)

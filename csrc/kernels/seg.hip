@@ -652,10 +652,25 @@ struct RootDraw {
   cdna::PoissonCdf cdf;
 };
 
+// MOVE (level 1 of a forest whose every root split, numerically): the codes still hold the level-0 local node
+// (0) -- the row partition of level 0 was not run.  The ring moves each row itself, exactly as partition7_kernel
+// would have: one coalesced byte load of the root split's feature from the column-major [G][n] bins words
+// (prefetched a window ahead with the code and the label), a compare against the split bin, and one coalesced
+// 2-byte store of (weight << 8 | child's local node, 0xFF = done) before the node test.  A (tree, row chunk) work
+// item is owned by one block and a block touches only its own tree's codes, so the update in place has no race;
+// every tree must have exactly one slot in the launch, or its codes would stay unmoved.  The HBM traffic (8 bytes
+// read and 2 written per row and tree) and the VALU work ride in the shadow of the LDS atomics.
+struct RootMove {
+  const uint8_t* bins;  // column-major bins [G][n][8]
+  int G, T;
+  const int *split_feat, *split_bin, *cat_off, *child, *tfirst_next;  // split_decode's tables, level 0 (A = T)
+};
+
 // One wave's ring of records compacted from the row codes (both root kernels).  RING entries of LDS; a trip
 // consumes up to NI of them, lane by lane: NI - 1 + 64 < RING, so a refill window never overwrites unread entries.
-template <int RING, int NI, bool DRAW>
+template <int RING, int NI, bool DRAW, bool MOVE = false>
 struct CodesRing {
+  static_assert(!(DRAW && MOVE), "the draws write level-0 codes: nothing to move");
   static_assert((RING & (RING - 1)) == 0 && NI - 1 + 64 < RING, "ring size");
   uint64_t* rg;
   const uint16_t* ct;  // the tree's codes
@@ -669,15 +684,33 @@ struct CodesRing {
   uint32_t head = 0u, tail = 0u;  // wave-uniform ring cursors
   uint32_t ncw = 0xFFu;  // the window in flight: the lane's row code and label
   float ny = 0.f;
+  // MOVE only: the tree's root split (wave-uniform) and the window in flight's split byte
+  const uint8_t* mbyte = nullptr;  // byte of the split feature in row 0's bins word (null: the root is a leaf)
+  uint32_t mbin = 0u, mleft = 0xFFu, mright = 0xFFu;  // split bin, the children's local nodes (0xFF: leaf)
+  uint32_t nbin = 0u;
 
   __device__ __forceinline__ CodesRing(uint64_t* ring_lds, const uint16_t* codes, int64_t n, const float* v1_,
                                        float qs1_, int tree_, uint32_t node_, int r0, int len, int wid, int nw,
-                                       const RootDraw* dr_)
+                                       const RootDraw* dr_, const RootMove* mv = nullptr)
       : rg(ring_lds), ct(codes + (int64_t)tree_ * n), v1(v1_), qs1(qs1_), tree(tree_), node(node_), dr(dr_),
         lane(threadIdx.x & 63) {
     const int per = ((len + nw - 1) / nw + 63) & ~63;
     wr = (int64_t)r0 + (int64_t)wid * per;
     wend = (int64_t)r0 + len < wr + per ? (int64_t)r0 + len : wr + per;
+    if (MOVE && CDNA_DCHECK(tree_ < mv->T, 0x5E87u)) {
+      // level 0: active node i is the root of tree i
+      const int f = mv->split_feat[tree_];
+      const int c0 = mv->child[2 * tree_], c1 = mv->child[2 * tree_ + 1], tfn = mv->tfirst_next[tree_];
+      // a split feature outside the bins, a bin-set split, a child outside the tree's next level
+      const bool ok = CDNA_DCHECK(f < 8 * mv->G && mv->cat_off[tree_] < 0 && c0 - tfn < 0xFF && c1 - tfn < 0xFF &&
+                                      (c0 < 0 || c0 >= tfn) && (c1 < 0 || c1 >= tfn), 0x5E87u);
+      if (f >= 0 && f < 8 * mv->G && ok) {
+        mbyte = mv->bins + ((int64_t)(f >> 3) * n) * 8 + (f & 7);
+        mbin = (uint32_t)mv->split_bin[tree_];
+        mleft = c0 >= 0 ? (uint32_t)(c0 - tfn) & 0xFFu : 0xFFu;
+        mright = c1 >= 0 ? (uint32_t)(c1 - tfn) & 0xFFu : 0xFFu;
+      }
+    }
     fetch(wr + lane);
   }
 
@@ -691,7 +724,18 @@ struct CodesRing {
     } else {
       ncw = r < wend ? (uint32_t)ct[r] : 0xFFu;
     }
+    if (MOVE) nbin = (r < wend && mbyte != nullptr) ? (uint32_t)mbyte[r * 8] : 0u;
     ny = r < wend ? v1[r] : 0.f;
+  }
+
+  // MOVE: the row's level-0 code -> its level-1 code (partition7_kernel's move for the root's split), stored back
+  __device__ __forceinline__ uint32_t moved(int64_t r, uint32_t cw, uint32_t bin) const {
+    const uint32_t loc = cw & 0xFFu;
+    if (loc == 0xFFu || !CDNA_DCHECK(loc == 0u, 0x5E88u)) return cw;  // done; a local node outside level 0
+    const uint32_t nl = mbyte == nullptr ? 0xFFu : (bin <= mbin ? mleft : mright);
+    const uint32_t res = (cw & 0xFF00u) | nl;
+    const_cast<uint16_t*>(ct)[r] = (uint16_t)res;
+    return res;
   }
 
   // Until the rows are exhausted and the ring drained: refill to NI entries, hand `body` the lane's U records of
@@ -700,11 +744,13 @@ struct CodesRing {
   __device__ __forceinline__ void for_each_trip(int first, int stride, bool on, F&& body) {
     for (;;) {
       while (tail - head < (uint32_t)NI && wr < wend) {  // wave-uniform refill, one 64-row window per round
-        const uint32_t cw = ncw;
+        uint32_t cw = ncw;
+        const uint32_t bin = nbin;
         const float y = ny;
         const int64_t r = wr + lane;
         wr += 64;
         fetch(wr + lane);
+        if (MOVE) cw = moved(r, cw, bin);
         const bool has = (cw & 0xFFu) == node && (cw >> 8) != 0u;
         const uint64_t m = __builtin_amdgcn_ballot_w64(has);
         if (has) {
@@ -730,12 +776,16 @@ struct CodesRing {
   }
 };
 
-template <int BP, bool DRAW>
+template <bool C, typename A, typename B> struct RootAuxT { using type = A; };
+template <typename A, typename B> struct RootAuxT<false, A, B> { using type = B; };
+
+// (aux: the RootMove tables of the MOVE instantiation, else the RootDraw arguments)
+template <int BP, bool DRAW, bool MOVE = false>
 __global__ __launch_bounds__(1024) void seg_hist_lane10_root_kernel(const SegHistArgs a, const uint8_t* __restrict__ bins8,
                                                                     const uint16_t* __restrict__ codes,
                                                                     const float* __restrict__ v1, float qs1,
                                                                     const int* __restrict__ sinfo, int slot0,
-                                                                    const RootDraw dr) {
+                                                                    const typename RootAuxT<MOVE, RootMove, RootDraw>::type aux) {
   using Tile = Lane10Tile<BP>;
   constexpr int NW = Tile::NW, U = 16, IPW = Tile::IPW, NI = IPW * U, RING = 256;
   __shared__ __attribute__((aligned(16))) unsigned long long h[Tile::CELLS];
@@ -748,7 +798,11 @@ __global__ __launch_bounds__(1024) void seg_hist_lane10_root_kernel(const SegHis
   clear_cells<Tile::CELLS>(h);
   const Tile t(bins8);
   const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  CodesRing<RING, NI, DRAW> rq(ring[wid], codes, a.n, v1, qs1, tree, node, r0, len, wid, NW, &dr);
+  const RootDraw* dr = nullptr;
+  const RootMove* mv = nullptr;
+  if constexpr (MOVE) mv = &aux;
+  else dr = &aux;
+  CodesRing<RING, NI, DRAW, MOVE> rq(ring[wid], codes, a.n, v1, qs1, tree, node, r0, len, wid, NW, dr, mv);
   rq.template for_each_trip<U>(t.item, IPW, t.on,
                                [&](const uint64_t(&rc)[U]) __attribute__((always_inline)) { t.trip(h, a, rc); });
   Tile::flush(h, a, slot - slot0);
@@ -1708,6 +1762,28 @@ CDNA_API int cdna_seg_hist_root(const uint8_t* bins_s10, int64_t n, int d, int B
     if (B <= 32) launch(seg_hist_lane10_root_kernel<32, false>);
     else launch(seg_hist_lane10_root_kernel<40, false>);
   }
+  return (int)hipGetLastError();
+}
+
+// Level 1 of a forest whose level-0 row partition was not run (RootMove): every slot is the one built child of its
+// tree's root, every tree has a slot, and the kernel moves the codes from level 0 to level 1 in place while it
+// compacts them.  bins_cm: the column-major bins words [G][n]; the tables are split_decode's of level 0 (T active
+// nodes, numeric splits only).
+CDNA_API int cdna_seg_hist_root_move(const uint8_t* bins_s10, int64_t n, int d, int B, uint16_t* codes,
+                                     const float* v1, float qs1, const int* work, int nwork, const int* sinfo,
+                                     int slot0, unsigned long long* out, const uint8_t* bins_cm, int G, int T,
+                                     const int* split_feat, const int* split_bin, const int* cat_off,
+                                     const int* child, const int* tfirst_next, int cls3, hipStream_t st) {
+  if (nwork <= 0) return 0;
+  if (d > 100 || B > 40 || B < 1 || G < (d + 7) / 8 || T < 1) return (int)hipErrorInvalidValue;
+  SegHistArgs a{nullptr, n, d, B, nullptr, nullptr, v1, nullptr, work, 1.f, qs1, out};
+  a.cls_split = cls3 ? kClsSplit : 0;
+  RootMove mv{bins_cm, G, T, split_feat, split_bin, cat_off, child, tfirst_next};
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwork), dim3(1024), 0, st, a, bins_s10, codes, v1, qs1, sinfo, slot0, mv);
+  };
+  if (B <= 32) launch(seg_hist_lane10_root_kernel<32, false, true>);
+  else launch(seg_hist_lane10_root_kernel<40, false, true>);
   return (int)hipGetLastError();
 }
 
