@@ -1,1 +1,2 @@
-from ..models.clustering import BisectingKMeans, KMeans, KMeansModel, KMeansSummary  # noqa: F401
+from ..models.clustering import (BisectingKMeans, GaussianMixture, GaussianMixtureModel,  # noqa: F401
+                                 GaussianMixtureSummary, KMeans, KMeansModel, KMeansSummary, MultivariateGaussian)

@@ -1,4 +1,4 @@
-"""Clustering: distributed k-means.
+"""Clustering: distributed k-means and Gaussian mixtures.
 
 Each Lloyd iteration = one pass of the K10 ``kmeans_step`` HIP kernel
 (nearest-centre assignment + LDS-privatised per-centre sums) and one RCCL
@@ -6,6 +6,10 @@ all-reduce of k*(d+1) doubles — the map → reduce → communicate pattern of
 MLE 02 - K-Means.py:178-204.  ``maxIter=0`` returns the initial centres
 (MLE 02:46-68).  Initialisation: k-means++ over a global sample
 ("k-means||" default) or random points, both seeded.
+
+``GaussianMixture`` is EM for a full-covariance mixture: each iteration is one pass of the K23 ``gmm_step`` op
+(responsibilities and centred moment sums, both on the fp32 MFMA), one all-reduce of k (d+1)^2 + 3 doubles and an
+M-step on the host in fp64.
 """
 from __future__ import annotations
 
@@ -17,9 +21,10 @@ from ..sql import types as T
 from ..sql.batch import ColumnData
 from ..sql.dataframe import MapPlan
 from .base import Estimator, Model
+from .linalg import DenseMatrix, DenseVector
 from .param import NO_DEFAULT, TypeConverters as TC, keyword_init
 from .regression import _default_seed
-from .util import global_count, global_offset, local_xyw, require_vector
+from .util import VECTOR_F64_MAX, IllegalArgumentException, global_count, global_offset, local_xyw, require_vector
 
 
 class KMeans(Estimator):
@@ -224,3 +229,237 @@ class BisectingKMeans(KMeans):
         model = KMeansModel(np.array(centers))
         model._post_fit(self)
         return model
+
+
+# ======================================================================================= GaussianMixture
+class MultivariateGaussian:
+    """``pyspark.ml.stat.distribution.MultivariateGaussian``: a mean vector and a covariance matrix."""
+
+    def __init__(self, mean, cov):
+        self.mean = mean if isinstance(mean, DenseVector) else DenseVector(np.asarray(mean, dtype=np.float64))
+        if not isinstance(cov, DenseMatrix):
+            c = np.asarray(cov, dtype=np.float64)
+            cov = DenseMatrix(c.shape[0], c.shape[1], c.T.reshape(-1))
+        self.cov = cov
+
+    def __repr__(self):
+        return f"MultivariateGaussian(mean={self.mean!r}, cov={self.cov!r})"
+
+
+def gmm_tables(weights, means, covs):
+    """(A [k, d, d], logc [k]) of ``K.gmm_step`` from the mixture's parameters, numpy fp64: A_j = D^-1/2 U^T over
+    the eigenpairs Spark's pseudo-inverse keeps (eigenvalue > eps d max eigenvalue; the dropped rows are zero),
+    logc_j = log pi_j - (d log 2 pi + log pdet Sigma_j) / 2."""
+    k, d = means.shape
+    A = np.zeros((k, d, d))
+    logc = np.zeros(k)
+    for j in range(k):
+        vals, vecs = np.linalg.eigh(covs[j])
+        tol = K.GMM_EPS * d * vals.max()
+        keep = vals > tol
+        if not keep.any():
+            raise ValueError(f"GaussianMixture: the covariance matrix of component {j} has no non-zero singular "
+                             f"values")
+        m = int(keep.sum())
+        A[j, :m] = vecs[:, keep].T / np.sqrt(vals[keep])[:, None]
+        with np.errstate(divide="ignore"):
+            logc[j] = np.log(weights[j]) - 0.5 * (d * np.log(2.0 * np.pi) + np.log(vals[keep]).sum())
+    return A, logc
+
+
+def _gmm_call(X, w, weights, means, covs, mode):
+    A, logc = gmm_tables(weights, means, covs)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
+    return K.gmm_step(X, w, t(means), t(A), t(logc), mode)
+
+
+_GMM_PARAMS = {
+    "featuresCol": ("features column name", "features", TC.toString),
+    "predictionCol": ("prediction column name", "prediction", TC.toString),
+    "probabilityCol": ("Column name for predicted class conditional probabilities.", "probability", TC.toString),
+    "k": ("Number of independent Gaussians in the mixture model. Must be > 1.", 2, TC.toInt),
+    "maxIter": ("max number of iterations (>= 0)", 100, TC.toInt),
+    "tol": ("the convergence tolerance for iterative algorithms (>= 0)", 0.01, TC.toFloat),
+    "seed": ("random seed", None, TC.toInt),
+    "aggregationDepth": ("suggested depth for treeAggregate (>= 2)", 2, TC.toInt),
+    "weightCol": ("weight column name", None, TC.toString),
+}
+
+
+class GaussianMixture(Estimator):
+    """EM for a mixture of full-covariance Gaussians (``pyspark.ml.clustering.GaussianMixture``): Spark's
+    initialisation, densities (pseudo-inverse of a singular covariance, EPSILON added to every density) and
+    stopping rule (absolute change of the total log-likelihood below ``tol``)."""
+    _params = _GMM_PARAMS
+
+    def __init__(self, featuresCol=None, predictionCol=None, k=None, probabilityCol=None, tol=None, maxIter=None,
+                 seed=None, aggregationDepth=None, weightCol=None):
+        super().__init__()
+        keyword_init(self, {k_: v for k_, v in locals().items() if k_ not in ("self", "__class__")})
+
+    def _init_state(self, session, X, k, seed):
+        """Spark's scheme on a seeded global sample (made as KMeans._init_centres makes its sample, so it is the
+        same at any rank count): 5 k rows drawn with replacement, component j gets the mean and the diagonal
+        variance of its 5 rows and weight 1 / k."""
+        comm = session.comm
+        n = X.shape[0]
+        ng = global_count(session, n)
+        off = global_offset(session, n)
+        if ng == 0:
+            raise ValueError("GaussianMixture: the training dataset is empty")
+        target = min(ng, max(20 * k, 10000))
+        frac = min(1.0, target / ng)
+        u = K.uniform(n, seed, off, 21, device=X.device)
+        samp = X[u < frac] if frac < 1 else X
+        if comm.distributed:
+            samp = torch.cat(comm.all_gather_varlen(samp.contiguous()))
+        S = samp.double().cpu().numpy()
+        if len(S) == 0:
+            raise ValueError("GaussianMixture: the initialisation sample is empty")
+        rng = np.random.default_rng(seed)
+        rows = S[rng.integers(len(S), size=5 * k)].reshape(k, 5, -1)
+        means = rows.mean(1)
+        covs = np.stack([np.diag(((rows[j] - means[j]) ** 2).mean(0)) for j in range(k)])
+        return np.full(k, 1.0 / k), means, covs
+
+    def _fit(self, dataset):
+        k = self.getK()
+        if k <= 1:
+            raise IllegalArgumentException(f"GaussianMixture parameter k given invalid value {k}: must be > 1")
+        X, _, w = local_xyw(dataset, self.getFeaturesCol(), None, self.getWeightCol() or None, keep_f64=True)
+        session = dataset._session
+        comm = session.comm
+        seed = self.getSeed() if self.getSeed() is not None else _default_seed(type(self))
+        d = X.shape[1]
+        D = d + 1
+        # before the initial state is drawn: a non-finite row among its 5 k draws would turn the initial means and
+        # variances into NaN and surface as a singular covariance
+        bad = (~torch.isfinite(X).all(1)).sum().double().reshape(1)
+        comm.all_reduce(bad)
+        if float(bad) > 0:
+            raise ValueError(f"GaussianMixture: {int(bad)} rows of column {self.getFeaturesCol()} have non-finite "
+                             f"values")
+        weights, means, covs = self._init_state(session, X, k, seed)
+
+        def sums(mode):
+            out = _gmm_call(X, w, weights, means, covs, mode)
+            S, st = out if mode == K.GMM_STEP else (None, out)
+            buf = st if S is None else torch.cat([S.reshape(-1), st])
+            comm.all_reduce(buf)
+            host = buf.cpu().numpy()
+            if host[-1] > 0:
+                raise ValueError(f"GaussianMixture: {int(host[-1])} rows of column {self.getFeaturesCol()} have a "
+                                 f"non-finite Mahalanobis distance (overflow)")
+            return (None if S is None else host[:-3].reshape(k, D, D)), host[-3:]
+
+        tol, max_iter = self.getTol(), self.getMaxIter()
+        ll, ll_prev, it = -np.finfo(np.float64).max, 0.0, 0
+        while it < max_iter and not abs(ll - ll_prev) < tol:
+            S, st = sums(K.GMM_STEP)
+            # the op centres component j at c_j: the mean it was given, rounded to fp32 for fp32 rows
+            c = means.astype(np.float32).astype(np.float64) if X.dtype == torch.float32 else means
+            N = S[:, d, d]
+            delta = S[:, :d, d] / N[:, None]
+            means = c + delta
+            covs = S[:, :d, :d] / N[:, None, None] - delta[:, :, None] * delta[:, None, :]
+            weights = N / N.sum()
+            ll_prev, ll = ll, float(st[0])
+            it += 1
+        if it == 0:
+            ll = float(sums(K.GMM_EVAL)[1][0])
+        model = GaussianMixtureModel(weights, means, covs)
+        model._post_fit(self)
+        if X.shape[0]:
+            assign = _gmm_call(X, None, weights, means, covs, K.GMM_PREDICT)[1]
+            sizes = torch.bincount(assign.long(), minlength=k).double()
+        else:
+            sizes = torch.zeros(k, dtype=torch.float64, device=X.device)
+        comm.all_reduce(sizes)
+        model.summary = GaussianMixtureSummary(model, dataset, ll, it, sizes.cpu().numpy().astype(np.int64).tolist())
+        return model
+
+
+class GaussianMixtureSummary:
+    def __init__(self, model, dataset, log_likelihood, iters, sizes):
+        self._model = model
+        self._dataset = dataset
+        self.logLikelihood = log_likelihood
+        self.numIter = iters
+        self.clusterSizes = sizes
+        self.k = len(sizes)
+        self.featuresCol = model.getFeaturesCol()
+        self.predictionCol = model.getPredictionCol()
+        self.probabilityCol = model.getProbabilityCol()
+
+    @property
+    def predictions(self):
+        return self._model.transform(self._dataset)
+
+    @property
+    def cluster(self):
+        return self.predictions.select(self.predictionCol)
+
+    @property
+    def probability(self):
+        return self.predictions.select(self.probabilityCol)
+
+
+class GaussianMixtureModel(Model):
+    _params = _GMM_PARAMS
+
+    def __init__(self, weights=None, means=None, covs=None):
+        super().__init__()
+        self._w = np.asarray(weights if weights is not None else np.zeros(0), dtype=np.float64)
+        self._mu = np.asarray(means if means is not None else np.zeros((0, 0)), dtype=np.float64)
+        self._cov = np.asarray(covs if covs is not None else np.zeros((0, 0, 0)), dtype=np.float64)
+        self.summary = None
+
+    @property
+    def weights(self):
+        return [float(v) for v in self._w]
+
+    @property
+    def gaussians(self):
+        return [MultivariateGaussian(m, c) for m, c in zip(self._mu, self._cov)]
+
+    @property
+    def hasSummary(self):
+        return self.summary is not None
+
+    def _responsibilities(self, features):
+        x = np.asarray(features.toArray() if hasattr(features, "toArray") else features, dtype=np.float64)
+        return _gmm_call(torch.from_numpy(x.reshape(1, -1).copy()), None, self._w, self._mu, self._cov,
+                         K.GMM_PREDICT)
+
+    def predict(self, features):
+        return int(self._responsibilities(features)[1][0])
+
+    def predictProbability(self, features):
+        return DenseVector(self._responsibilities(features)[0][0].numpy())
+
+    def _transform(self, dataset):
+        fc, pc, prc = self.getFeaturesCol(), self.getPredictionCol(), self.getProbabilityCol()
+        require_vector(dataset, fc)
+        A, logc = gmm_tables(self._w, self._mu, self._cov)
+        mu, A, logc = torch.tensor(self._mu), torch.tensor(A), torch.tensor(logc)
+        prep = K.GmmPrepared(mu, A, logc)   # the device tables are built once, not per batch
+
+        def fn(b, ctx):
+            X = b.columns[fc].values
+            X = X if X.dtype == torch.float64 and X.numel() <= VECTOR_F64_MAX else X.float()
+            R, a, _ = K.gmm_step(X, None, mu, A, logc, K.GMM_PREDICT, prepared=prep)
+            if pc:
+                b = b.with_column(pc, ColumnData(a.to(torch.int32), T.IntegerType()))
+            if prc:
+                b = b.with_column(prc, ColumnData(R, T.VectorUDT()))
+            return b
+        return dataset._new(MapPlan(dataset._plan, "GaussianMixtureModel", fn))
+
+    def _save_state(self):
+        return {}, {"weights": torch.tensor(self._w), "means": torch.tensor(self._mu), "covs": torch.tensor(self._cov)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._w = tensors["weights"].numpy()
+        self._mu = tensors["means"].numpy()
+        self._cov = tensors["covs"].numpy()
+        self.summary = None

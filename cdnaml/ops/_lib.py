@@ -234,6 +234,12 @@ _SIGS = {
     "cdna_glm_step": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                        c_float, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p], c_int),
+    "cdna_gmm_dk": ([c_int], c_int),
+    "cdna_gmm_dc": ([c_int], c_int),
+    "cdna_gmm_step_blocks": ([c_int64], c_int),
+    "cdna_gmm_step_workspace": ([c_int64, c_int, c_int], c_int64),
+    "cdna_gmm_step": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

@@ -1814,6 +1814,146 @@ def glm_step(X: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], offset
     return A.T @ A, stats
 
 
+# ------------------------------------------------------------ K23 gmm_step (gmm.hip)
+GMM_STEP, GMM_PREDICT, GMM_EVAL = 0, 1, 2
+GMM_EPS = 2.0 ** -52   # Spark's EPSILON: added to every component density
+GMM_MAX_D = 127        # the fused kernels' range: d + 1 <= 128
+GMM_MAX_K = 32         # and 2 <= k <= 32
+GMM_HOST_CHUNK = 1 << 18   # rows per pass of the host formulation (bounds its [rows, d] intermediates)
+
+
+def gmm_centres(mu: torch.Tensor, A: torch.Tensor, f32: bool):
+    """(c, A', corr) of the op's definition, fp64 tensors: the centres, the matrices as the products use them
+    and the constant A'_j (mu_j - c_j).  For fp32 X the centres and the matrices are rounded to fp32."""
+    mu, A = mu.double(), A.double()
+    if not f32:
+        return mu, A, torch.zeros(mu.shape, dtype=torch.float64, device=mu.device)
+    c, Ar = mu.float().double(), A.float().double()
+    return c, Ar, torch.einsum("jab,jb->ja", Ar, mu - c)
+
+
+class GmmPrepared:
+    """The parameters of one mixture as ``gmm_step`` consumes them, prepared once per (device, row dtype, path)
+    and reused by every call that is given this object: a model's transform goes through the op once per batch."""
+
+    def __init__(self, mu: torch.Tensor, A: torch.Tensor, logc: torch.Tensor):
+        self.mu, self.A, self.logc = mu.double(), A.double(), logc.double()
+        self._made = {}
+
+    def on(self, dev, f32: bool, native: bool):
+        """(c, A', corr, logc) on ``dev``; for the native path (cf, AT, corr, logc): the kernels' zero-padded
+        fp32 centres [k, dk], transposed matrices [k, dk, dc] and fp64 constants [k, dc]."""
+        key = (str(dev), f32, native)
+        if key not in self._made:
+            c, Ar, corr = gmm_centres(self.mu.to(dev), self.A.to(dev), f32)
+            lc = self.logc.to(dev).contiguous()
+            if native:
+                k, d = c.shape
+                L = _lib.lib()
+                dk, dc = L.cdna_gmm_dk(d), L.cdna_gmm_dc(d)
+                cf = torch.zeros((k, dk), dtype=torch.float32, device=dev)
+                cf[:, :d] = c
+                AT = torch.zeros((k, dk, dc), dtype=torch.float32, device=dev)
+                AT[:, :d, :d] = Ar.transpose(1, 2)
+                cr = torch.zeros((k, dc), dtype=torch.float64, device=dev)
+                cr[:, :d] = corr
+                self._made[key] = (cf, AT, cr, lc)
+            else:
+                self._made[key] = (c, Ar, corr, lc)
+        return self._made[key]
+
+
+def gmm_step(X: torch.Tensor, w: Optional[torch.Tensor], mu: torch.Tensor, A: torch.Tensor, logc: torch.Tensor,
+             mode: int = GMM_STEP, native: bool = True, prepared: Optional[GmmPrepared] = None):
+    """One EM pass of a full-covariance Gaussian mixture over the local rows.
+
+    X [n, d] fp32 or fp64, w [n] fp64 row weights or None, mu [k, d], A [k, d, d] with q_j(x) = |A_j (x - mu_j)|^2,
+    logc [k] = log pi_j - (d log 2 pi + log pdet Sigma_j) / 2; all fp64.  Per row, in fp64 (Spark's formulas):
+    p_j = GMM_EPS + exp(logc_j - q_j / 2), s = sum_j p_j, r_j = p_j / s; a row that underflows under every
+    component gets uniform responsibilities.
+
+    GMM_STEP returns (S [k, d+1, d+1], stats [3]): S_j = sum_rows w r_j [t | 1][t | 1]^T with t = x - c_j, c_j the
+    centre the op uses (mu_j rounded to fp32 for fp32 X, mu_j itself for fp64 X), so new mean = c_j + S_j[:d, d] /
+    N_j and new covariance = S_j[:d, :d] / N_j - delta delta^T with a small delta; stats = [sum w log s, sum w,
+    rows whose q is not finite].  Such rows are left out of S and of the sums.
+    GMM_PREDICT returns (R [n, k] fp64, assign [n] int32, stats): assign is the argmax of R, lowest index among
+    equals; a left-out row has NaN responsibilities and assign 0.  GMM_EVAL returns stats.
+
+    fp32 X is defined with this rounding, on the device and in the host formulation alike: t is the fp32
+    difference, A_j is rounded to fp32, the constant A_j (mu_j - c_j) is subtracted from A_j t (the density is that
+    of the fp64 mean), the row scaled by fp32 sqrt(w r_j) is rounded to fp32 before the moment product, and
+    everything from q on is fp64.  fp64 X is fp64 throughout.
+
+    fp32 X on a GPU with d <= GMM_MAX_D and 2 <= k <= GMM_MAX_K (any n >= 1, row stride and alignment) runs the
+    K23 kernels: both products on the exact-fp32 MFMA, partial sums reduced in a fixed order, so two calls on the
+    same input return the same bits; N_j = S_j[d, d] is summed there in fp64 from the unrounded w r_j.  Everything
+    else takes the host formulation: the same formulas as torch ops (``native=False`` asks for it inside the range
+    too: bench/gmm_micro.py times the two side by side).  ``prepared``: a GmmPrepared of the same (mu, A, logc),
+    so that repeated calls with one mixture build its device tables once.
+    """
+    n, d = X.shape
+    k = mu.shape[0]
+    dev = X.device
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    f32 = X.dtype == torch.float32
+    wd = None if w is None else w.double().to(dev).contiguous()
+    prep = prepared if prepared is not None else GmmPrepared(mu, A, logc)
+    if native and _native(X) and f32 and 1 <= d <= GMM_MAX_D and 2 <= k <= GMM_MAX_K and n >= 1:
+        X = X if X.stride(1) == 1 and X.stride(0) >= d else X.contiguous()
+        L = _lib.lib()
+        cf, AT, cr, lc = prep.on(dev, True, True)
+        # every entry of S and of stats is written by the reduction
+        sws = torch.empty((3 + k) * L.cdna_gmm_step_blocks(n), dtype=torch.float64, device=dev)
+        stats = torch.empty(3, dtype=torch.float64, device=dev)
+        S = R = assign = ws = None
+        if mode == GMM_STEP:
+            S = torch.empty((k, d + 1, d + 1), dtype=torch.float64, device=dev)
+            ws = torch.empty(L.cdna_gmm_step_workspace(n, d, k), dtype=torch.float32, device=dev)
+        elif mode == GMM_PREDICT:
+            R = torch.empty((n, k), dtype=torch.float64, device=dev)
+            assign = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(L.cdna_gmm_step(_ptr(X), n, d, X.stride(0), _ptr(wd), _ptr(cf), _ptr(AT), _ptr(cr), _ptr(lc), k,
+                                   int(mode), _ptr(S), _ptr(R), _ptr(assign), _ptr(stats), _ptr(ws), _ptr(sws),
+                                   _stream(dev)), "cdna_gmm_step")
+        return (S, stats) if mode == GMM_STEP else ((R, assign, stats) if mode == GMM_PREDICT else stats)
+    # host formulation, GMM_HOST_CHUNK rows at a time
+    c, Ar, corr, lc = prep.on(dev, f32, False)
+    S = torch.zeros((k, d + 1, d + 1), dtype=torch.float64, device=dev)
+    stats = torch.zeros(3, dtype=torch.float64, device=dev)
+    Rs, As = [], []
+    cx = c.to(X.dtype)
+    Ax = Ar.to(X.dtype)
+    for i0 in range(0, n, GMM_HOST_CHUNK):
+        Xc = X[i0:i0 + GMM_HOST_CHUNK]
+        wc = torch.ones(Xc.shape[0], dtype=torch.float64, device=dev) if wd is None else wd[i0:i0 + GMM_HOST_CHUNK]
+        q = torch.stack([(((Xc - cx[j]) @ Ax[j].T).double() - corr[j]).square().sum(1) for j in range(k)], 1)
+        bad = ~torch.isfinite(q).all(1)
+        p = GMM_EPS + torch.exp(lc - 0.5 * q)
+        s = p.sum(1)
+        r = p / s[:, None]
+        zero = torch.zeros_like(s)
+        stats += torch.stack([torch.where(bad, zero, wc * torch.log(s)).sum(), torch.where(bad, zero, wc).sum(),
+                              bad.sum().double()])
+        if mode == GMM_PREDICT:
+            Rs.append(torch.where(bad[:, None], torch.full_like(r, float("nan")), r))
+            As.append(torch.where(bad, torch.zeros_like(bad, dtype=torch.int64), torch.argmax(r, 1)).to(torch.int32))
+        elif mode == GMM_STEP:
+            sr = torch.sqrt(torch.where(bad[:, None], torch.zeros_like(r), wc[:, None] * r)).to(X.dtype)
+            for j in range(k):
+                sj = sr[:, j:j + 1]
+                Z = torch.cat([torch.where(sj != 0, (Xc - cx[j]) * sj, torch.zeros_like(Xc)), sj], 1).double()
+                S[j] += Z.T @ Z
+    if mode == GMM_STEP:
+        return S, stats
+    if mode == GMM_PREDICT:
+        if not Rs:
+            return (torch.zeros((0, k), dtype=torch.float64, device=dev),
+                    torch.zeros(0, dtype=torch.int32, device=dev), stats)
+        return torch.cat(Rs), torch.cat(As), stats
+    return stats
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
