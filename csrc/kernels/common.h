@@ -55,6 +55,9 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// neither inf nor NaN
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
 // ---------------------------------------------------------------------------
 // Philox4x32-10 counter-based RNG.  Keyed by a 64-bit seed, countered by a
 // 64-bit element index plus a 32-bit stream id.  Because the counter is the

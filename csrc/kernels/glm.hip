@@ -25,9 +25,11 @@
 // zeroed, so an inf / NaN feature that made eta non-finite does not reach G.  (INIT does not form eta from the
 // features; a non-finite feature goes into G as it is there, and the next step counts the row.)
 // Native range: d + 2 <= 128.
-#include "common.h"
+#include "symtile.h"
 
 namespace {
+
+using namespace symtile;
 
 constexpr double kEps = 1e-16;
 constexpr int kRows = 64;
@@ -128,8 +130,6 @@ __device__ __forceinline__ double glm_init_mu(const GlmSpec& s, double y, double
   return y;
 }
 
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
 // One row's IRLS terms.  Kept out of line: inlined, the fp64 link / variance / deviance bodies of every family
 // (pow, normcdfinv, ...) pushed the streaming kernel past its register budget and into scratch.
 struct RowTerms {
@@ -149,20 +149,9 @@ __device__ __noinline__ RowTerms glm_row(GlmSpec sp, int mode, double y, double 
   RowTerms r;
   r.W = w / (glm_variance(sp, mu) * gp * gp);
   r.z = eta - off + (y - mu) * gp;
-  r.fin = (finite_d(mu) && finite_d(r.W) && finite_d(r.z)) ? 1.0 : 0.0;
+  r.fin = (cdna::finite_d(mu) && cdna::finite_d(r.W) && cdna::finite_d(r.z)) ? 1.0 : 0.0;
   r.dev = r.fin != 0.0 ? glm_unit_dev(sp, y, mu) : 0.0;
   return r;
-}
-
-// upper-triangular tile pair p of a T x T tile grid, row-major: (0,0), (0,1), ..
-__device__ __host__ __forceinline__ void pair_ij(int p, int T, int& I, int& J) {
-  int i = 0;
-  while (p >= T - i) {
-    p -= T - i;
-    ++i;
-  }
-  I = i;
-  J = i + p;
 }
 
 // VW = 4: float4 row loads (d % 4 == 0, ldx % 4 == 0, 16-byte aligned X); VW = 1: scalar loads, any layout.
@@ -192,14 +181,7 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : 1) void glm_step_kernel(
     beta_s[i] = (i < d && beta != nullptr) ? beta[i] : 0.0;
     shift_s[i] = (i < d && shift != nullptr) ? shift[i] : 0.f;
   }
-  int TI[PW], TJ[PW];
-  bool own[PW];
-#pragma unroll
-  for (int j = 0; j < PW; ++j) {
-    const int p = wid + 4 * j;
-    own[j] = p < npairs;
-    pair_ij(own[j] ? p : 0, T, TI[j], TJ[j]);
-  }
+  const WavePairs<PW> wp(wid, T, npairs);
   f32x16 acc[PW];
 #pragma unroll
   for (int j = 0; j < PW; ++j)
@@ -214,7 +196,9 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : 1) void glm_step_kernel(
   double yv = 0.0, wv = 0.0, ov = 0.0;
   double s_dev = 0.0, s_w = 0.0, s_wy = 0.0, s_bad = 0.0;
 
-// next tile's rows -> registers (rows past rb1 become zeros with weight 0)
+// Next tile's rows -> registers (rows past rb1 become zeros with weight 0), then registers -> LDS.  Kept here as
+// macros: written through symtile::RowTile (as K23 does) the float4 kernels take 200 / 217 / 249 VGPRs for 196 /
+// 216 / 234 and EVAL measured 0.3 % slower (profiles/r11/symtile.md).
 #define GLM_LOAD(T0)                                                                   \
   {                                                                                    \
     const int64_t lim_ = rb1 - (T0);                                                   \
@@ -284,17 +268,7 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : 1) void glm_step_kernel(
         row[d + 1] = (float)(sw * (z - (double)zshift));
       }
       __syncthreads();  // scaled tile complete
-      const float* tc = buf + cur * tsz + half * LD + col;
-#pragma unroll 4
-      for (int k = 0; k < kRows; k += 2) {
-        const float* rp = tc + k * LD;
-#pragma unroll
-        for (int j = 0; j < PW; ++j) {
-          if (!own[j]) continue;
-          const float a = rp[32 * TI[j]], b = rp[32 * TJ[j]];
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[j], 0, 0, 0);
-        }
-      }
+      mfma_rows<kRows>(wp, buf + cur * tsz + half * LD + col, LD, acc);
     }
     if (more) GLM_STORE(buf + (cur ^ 1) * tsz);
     cur ^= 1;
@@ -304,12 +278,8 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : 1) void glm_step_kernel(
 
   if (mode != kEval) {
 #pragma unroll
-    for (int j = 0; j < PW; ++j) {
-      if (!own[j]) continue;
-      float* dst = partial + ((int64_t)blockIdx.x * npairs + wid + 4 * j) * 1024;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dst[((e & 3) + 8 * (e >> 2) + 4 * half) * 32 + col] = acc[j][e];
-    }
+    for (int j = 0; j < PW; ++j)
+      if (wp.own[j]) store_slab(partial + ((int64_t)blockIdx.x * npairs + wid + 4 * j) * 1024, acc[j], half, col);
   }
   // the block's scalars: wave butterflies, then the 4 waves in order
   s_dev = cdna::wave_sum(s_dev);
@@ -327,7 +297,7 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : 1) void glm_step_kernel(
 }
 
 // Blocks 0 .. gridDim.x - 2: partial [nblk][npairs][1024] -> G (symmetric fill), 16 threads per element each
-// summing a fixed stride of blocks, then a fixed-order sum (as gram_reduce_kernel).  Last block: the scalars,
+// summing a fixed stride of blocks, then a fixed-order sum (symtile::reduce_slabs).  Last block: the scalars,
 // spart [nblk][4] -> stats[4], the same way.
 __global__ __launch_bounds__(256) void glm_reduce_kernel(const float* __restrict__ partial, int nblk, int npairs,
                                                          int T, int D, double* __restrict__ G,
@@ -349,26 +319,8 @@ __global__ __launch_bounds__(256) void glm_reduce_kernel(const float* __restrict
     }
     return;
   }
-  const int64_t idx = (int64_t)blockIdx.x * 16 + el;
-  const bool ok = idx < (int64_t)npairs * 1024;
-  const int gp = ok ? (int)(idx >> 10) : 0, e = ok ? (int)(idx & 1023) : 0;
-  double s = 0.0;
-  if (ok)
-    for (int b = part; b < nblk; b += 16) s += (double)partial[((int64_t)b * npairs + gp) * 1024 + e];
-  red[part][el] = s;
-  __syncthreads();
-  if (part == 0 && ok) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += red[k][el];
-    int I, J;
-    pair_ij(gp, T, I, J);
-    const int i = I * 32 + (e >> 5), j = J * 32 + (e & 31);
-    if (i < D && j < D) {
-      G[(int64_t)i * D + j] = t;
-      G[(int64_t)j * D + i] = t;
-    }
-  }
+  reduce_slabs(red, partial, npairs, nblk, npairs, [T](int p, int& I, int& J) { pair_ij(p, T, I, J); }, D, G,
+               [](int, int) { return false; });
 }
 
 struct GlmPlan {
@@ -399,13 +351,9 @@ int glm_launch(const GlmPlan& pl, const float* X, int64_t n, int d, int64_t ldx,
   // the dynamic LDS passes the 64 KB default at d + 2 > 96: raised to the widest plan's size, once per
   // instantiation and device
   static bool raised[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || !raised[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(glm_step_kernel<PW, VW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)glm_plan(1, kMaxD - 2).lds);
-    if (e != hipSuccess) return (int)e;
-    if (dev >= 0 && dev < 64) raised[dev] = true;
-  }
+  const int rc = raise_lds(reinterpret_cast<const void*>(glm_step_kernel<PW, VW>), raised,
+                           glm_plan(1, kMaxD - 2).lds);
+  if (rc != 0) return rc;
   hipLaunchKernelGGL((glm_step_kernel<PW, VW>), dim3(pl.nblk), dim3(256), pl.lds, st, X, n, d, ldx, y, w, off, beta,
                      b0, shift, zshift, sp, mode, pl.T, pl.npairs, pl.LD, ws, sws, pl.rows_per_block);
   return (int)hipGetLastError();
@@ -444,7 +392,7 @@ CDNA_API int cdna_glm_step(const float* X, int64_t n, int d, int64_t ldx, const 
     return (int)hipErrorInvalidValue;
   const GlmPlan pl = glm_plan(n, d);
   const GlmSpec sp{family, link, var_power, link_power};
-  const bool vec = d % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  const bool vec = float4_rows(X, d, ldx);
   const int rc = vec ? glm_launch_pw<4>(pl, X, n, d, ldx, y, w, off, beta, b0, shift, zshift, sp, mode, ws, sws, st)
                      : glm_launch_pw<1>(pl, X, n, d, ldx, y, w, off, beta, b0, shift, zshift, sp, mode, ws, sws, st);
   if (rc != 0) return rc;

@@ -21,17 +21,19 @@
 // XCD-remapped launch order so their re-reads of the chunk's rows meet in one L2 (the plan keeps the number of
 // chunks a multiple of 8 from 8 chunks on, so no chunk straddles two XCDs; below 8 chunks some do).  The tile is
 // centred at c_j and scaled by fp32 √(w r_j) on its way into LDS (the tile's 64 scales are prefetched with its rows
-// and staged in LDS), with the scale itself as column d; K22's MFMA phase over the upper triangular 32x32 tile
-// pairs of the (d+1)x(d+1) moment matrix; two levels of accumulators held for the whole chunk (fp32 within a tile,
-// fp64 across tiles), one fp64 slab per block.  N_j = S_j[d][d] is not taken from the slabs: the E-step sums w r_j
-// in fp64.
+// and staged in LDS), with the scale itself as column d; symtile.h's MFMA phase (K22's) over the upper triangular
+// 32x32 tile pairs of the (d+1)x(d+1) moment matrix; two levels of accumulators held for the whole chunk (fp32 within
+// a tile, fp64 across tiles), one fp64 slab per block.  N_j = S_j[d][d] is not taken from the slabs: the E-step sums
+// w r_j in fp64.
 //
 // gmm_reduce_kernel: slabs and per-block scalars in a fixed order in fp64.  No float atomics on global memory: two
 // calls on the same input return the same bits.
 // Native range: d + 1 <= 128, 2 <= k <= 32.
-#include "common.h"
+#include "symtile.h"
 
 namespace {
+
+using namespace symtile;
 
 constexpr int kRows = 64;
 constexpr int kMaxD = 128;  // d + 1 <= kMaxD
@@ -39,30 +41,6 @@ constexpr int kMaxK = 32;
 constexpr double kGmmEps = 2.220446049250313e-16;  // 2^-52, Spark's EPSILON
 
 enum { kStep = 0, kPredict = 1, kEval = 2 };
-
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
-
-// upper-triangular tile pair p of a T x T tile grid, row-major: (0,0), (0,1), ..
-__device__ __host__ __forceinline__ void pair_ij(int p, int T, int& I, int& J) {
-  int i = 0;
-  while (p >= T - i) {
-    p -= T - i;
-    ++i;
-  }
-  I = i;
-  J = i + p;
-}
-
-// The next tile's rows -> registers (rows past rb1 become zeros).  e_ indexes (row, load item) of the 64-row tile.
-#define GMM_LOAD_X(T0)                                                                 \
-  _Pragma("unroll") for (int i = 0; i < kNI; ++i) {                                    \
-    const int e_ = tid + 256 * i;                                                      \
-    const int r_ = e_ / dv, c_ = e_ - r_ * dv;                                         \
-    vec_t t_ = {};                                                                     \
-    if (e_ < items && r_ < rb1 - (T0))                                                 \
-      t_ = *reinterpret_cast<const vec_t*>(X + ((T0) + r_) * ldx + (int64_t)c_ * VW);  \
-    v[i] = t_;                                                                         \
-  }
 
 // VW = 4: float4 row loads (d % 4 == 0, ldx % 4 == 0, 16-byte aligned X); VW = 1: scalar loads, any layout.
 // The kernel fills the register file: one block per CU.
@@ -73,14 +51,11 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
     const double* __restrict__ logc, int k, int mode, int dk, int dc, int LD, float* __restrict__ sr,
     double* __restrict__ R, int* __restrict__ assign, double* __restrict__ spart, int64_t rows_per_block) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int kNI = 32 / VW;  // items per thread: 64 rows x (d / VW) <= 64 * 128 / VW over 256 threads
-  typedef float vec_t __attribute__((ext_vector_type(VW)));
   float* tile = reinterpret_cast<float*>(smem);                            // [kRows][LD]
   double* qtab = reinterpret_cast<double*>(smem + (size_t)kRows * LD * 4);  // [2][kRows][k]
   double* red = qtab + 2 * kRows * k;                                       // [4][3 + kMaxK]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, half = lane >> 5, col = lane & 31;
   const int dv = d / VW;
-  const int items = kRows * dv;
   const int Tc = dc >> 5;
   const int rb = wid & 1, cb0 = wid >> 1, cb1 = cb0 + 2;
   const bool own0 = cb0 < Tc, own1 = cb1 < Tc;
@@ -92,7 +67,7 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
   int64_t rb1 = rb0 + rows_per_block;
   if (rb1 > n) rb1 = n;
   const int rr = tid >> 2, qq = tid & 3;  // row phase: 4 threads per row
-  vec_t v[kNI];
+  RowTile<VW> xt;
   double wv = 0.0;
   double s_ll = 0.0, s_w = 0.0, s_bad = 0.0;
   double nj[kMaxK / 4];  // STEP: this thread's share of N_j = sum w r_j, j = qq + 4 i
@@ -100,7 +75,7 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
   for (int i = 0; i < kMaxK / 4; ++i) nj[i] = 0.0;
 
   if (rb0 < rb1) {
-    GMM_LOAD_X(rb0);
+    xt.load(X, rb0, ldx, rb1 - rb0, tid, dv);
     wv = (rr < rb1 - rb0) ? (w != nullptr ? w[rb0 + rr] : 1.0) : 0.0;
   }
   for (int64_t t0 = rb0; t0 < rb1; t0 += kRows) {
@@ -108,17 +83,9 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
     const double rw = wv;
     const bool valid = t0 + rr < rb1;
     __syncthreads();  // every wave is past the MFMAs on the previous tile (and the zeroing, the first time)
-#pragma unroll
-    for (int i = 0; i < kNI; ++i) {
-      const int e_ = tid + 256 * i;
-      const int r_ = e_ / dv, c_ = e_ - r_ * dv;
-      if (e_ < items) {
-#pragma unroll
-        for (int u = 0; u < VW; ++u) tile[r_ * LD + c_ * VW + u] = v[i][u];
-      }
-    }
+    xt.store(tile, LD, tid, dv, [](int, int, float x) { return x; });  // odd LD: scalar stores
     if (more) {
-      GMM_LOAD_X(t0 + kRows);
+      xt.load(X, t0 + kRows, ldx, rb1 - (t0 + kRows), tid, dv);
       wv = (rr < rb1 - (t0 + kRows)) ? (w != nullptr ? w[t0 + kRows + rr] : 1.0) : 0.0;
     }
     __syncthreads();  // tile complete
@@ -165,8 +132,7 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
       }
       sq[0] += __shfl_xor(sq[0], 1);
       if ((col & 1) == 0) {
-        const int e = col >> 1;  // accumulator element whose row this lane holds
-        const int row = 32 * rb + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const int row = 32 * rb + acc_row(col >> 1, half);  // col >> 1: the accumulator element this lane holds
         qtab[((int64_t)cb0 * kRows + row) * k + j] = sq[0];
       }
     }
@@ -181,7 +147,7 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
       p[i] = 0.0;
       if (j < k) {
         const double qv = qtab[rr * k + j] + qtab[(kRows + rr) * k + j];
-        if (!finite_d(qv)) bad = true;
+        if (!cdna::finite_d(qv)) bad = true;
         p[i] = kGmmEps + exp(logc[j] - 0.5 * qv);
         s += p[i];
       }
@@ -264,22 +230,20 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
         ((red[tid] + red[kNS + tid]) + red[2 * kNS + tid]) + red[3 * kNS + tid];
 }
 
-// PW: tile pairs per wave; VW as above.  One block per CU here too; the scalar-load variant with 2 or 3 tile pairs
-// per wave also spills about half a KB per lane to scratch (32 loads in flight per thread), the float4 variants none.
+// PW: tile pairs per wave; VW as above.  One block per CU here too (PW = 1 with float4 loads fits two).  No
+// instantiation uses scratch: the scalar-load variants' 32 loads in flight per thread and the two levels of
+// accumulators go to 108-238 AGPRs instead (resource table: profiles/r11/symtile.md).
 template <int PW, int VW>
 __global__ __launch_bounds__(256) void gmm_moment_kernel(
     const float* __restrict__ X, int64_t n, int d, int64_t ldx, const float* __restrict__ sr, int k,
     const float* __restrict__ cf, int dk, int T, int npairs, int LD, double* __restrict__ partial,
     int64_t rows_per_chunk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int kNI = 32 / VW;
-  typedef float vec_t __attribute__((ext_vector_type(VW)));
   float* tile = reinterpret_cast<float*>(smem);  // [kRows][LD]
   float* cs = tile + kRows * LD;                 // [kMaxD]
   float* ss = cs + kMaxD;                        // [kRows]: the tile rows' scales
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, half = lane >> 5, col = lane & 31;
   const int dv = d / VW;
-  const int items = kRows * dv;
   // an XCD's work items are consecutive: the k components of a chunk run on one XCD whenever that XCD's share of the
   // grid is a multiple of k (gmm_plan: always from 8 chunks on)
   const uint32_t work = cdna::xcd_remap(blockIdx.x, gridDim.x);
@@ -288,14 +252,7 @@ __global__ __launch_bounds__(256) void gmm_moment_kernel(
 
   for (int i = tid; i < kRows * LD; i += 256) tile[i] = 0.f;
   for (int i = tid; i < kMaxD; i += 256) cs[i] = i < d ? cf[(int64_t)j * dk + i] : 0.f;
-  int TI[PW], TJ[PW];
-  bool own[PW];
-#pragma unroll
-  for (int q = 0; q < PW; ++q) {
-    const int p = wid + 4 * q;
-    own[q] = p < npairs;
-    pair_ij(own[q] ? p : 0, T, TI[q], TJ[q]);
-  }
+  const WavePairs<PW> wp(wid, T, npairs);
   // two levels of accumulators: the MFMAs add into the fp32 `acc` for kFoldRows rows, then `acc` is folded into the
   // fp64 `tot`.  A chunk-long fp32 chain carries about 3.5e-8 sqrt(roundings / 3) of a sum of positive terms, 1e-6
   // at 4096 rows, and EM's early iterations amplify a perturbation of the moments some 50 times: on the 20000 x 20
@@ -316,49 +273,28 @@ __global__ __launch_bounds__(256) void gmm_moment_kernel(
   const int64_t rb0 = chunk * rows_per_chunk;
   int64_t rb1 = rb0 + rows_per_chunk;
   if (rb1 > n) rb1 = n;
-  vec_t v[kNI];
+  RowTile<VW> xt;
   float s1 = 0.f;  // threads 0 .. 63: the scale of tile row tid, prefetched with the rows
+  auto load = [&](int64_t T0) __attribute__((always_inline)) {
+    xt.load(X, T0, ldx, rb1 - T0, tid, dv);
+    s1 = (tid < kRows && tid < rb1 - T0) ? sr[(T0 + tid) * k + j] : 0.f;
+  };
 
-#define GMM_LOAD_S(T0) s1 = (tid < kRows && tid < rb1 - (T0)) ? sr[((T0) + tid) * k + j] : 0.f;
-
-  if (rb0 < rb1) {
-    GMM_LOAD_X(rb0);
-    GMM_LOAD_S(rb0);
-  }
+  if (rb0 < rb1) load(rb0);
   for (int64_t t0 = rb0; t0 < rb1; t0 += kRows) {
     const bool more = t0 + kRows < rb1;
     if (tid < kRows) ss[tid] = s1;  // its readers of the previous tile are past that tile's second barrier
     __syncthreads();  // every wave is past the MFMAs on the previous tile (and the zeroing, the first time)
-#pragma unroll
-    for (int i = 0; i < kNI; ++i) {
-      const int e_ = tid + 256 * i;
-      const int r_ = e_ / dv, c_ = e_ - r_ * dv;
-      if (e_ < items) {
-        // a row with scale 0 (left out, zero weight, past the end) is zeroed, not scaled: NaN / inf stay out of S
-        const float sc = ss[r_];
-#pragma unroll
-        for (int u = 0; u < VW; ++u)
-          tile[r_ * LD + c_ * VW + u] = sc != 0.f ? (v[i][u] - cs[c_ * VW + u]) * sc : 0.f;
-      }
-    }
+    // a row with scale 0 (left out, zero weight, past the end) is zeroed, not scaled: NaN / inf stay out of S
+    xt.store(tile, LD, tid, dv, [&](int r, int c, float x) {
+      const float sc = ss[r];
+      return sc != 0.f ? (x - cs[c]) * sc : 0.f;
+    });
     if (tid < kRows) tile[tid * LD + d] = s1;
-    if (more) {
-      GMM_LOAD_X(t0 + kRows);
-      GMM_LOAD_S(t0 + kRows);
-    }
+    if (more) load(t0 + kRows);
     __syncthreads();  // scaled tile complete
-    const float* tc = tile + half * LD + col;
     for (int r0 = 0; r0 < kRows; r0 += kFoldRows) {
-#pragma unroll 4
-      for (int r = 0; r < kFoldRows; r += 2) {
-        const float* rp = tc + (r0 + r) * LD;
-#pragma unroll
-        for (int q = 0; q < PW; ++q) {
-          if (!own[q]) continue;
-          const float a = rp[32 * TI[q]], b = rp[32 * TJ[q]];
-          acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[q], 0, 0, 0);
-        }
-      }
+      mfma_rows<kFoldRows>(wp, tile + (r0 + half) * LD + col, LD, acc);
 #pragma unroll
       for (int q = 0; q < PW; ++q)
 #pragma unroll
@@ -368,17 +304,11 @@ __global__ __launch_bounds__(256) void gmm_moment_kernel(
         }
     }
   }
-#undef GMM_LOAD_S
 
 #pragma unroll
-  for (int q = 0; q < PW; ++q) {
-    if (!own[q]) continue;
-    double* dst = partial + ((chunk * k + j) * npairs + wid + 4 * q) * 1024;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) dst[((e & 3) + 8 * (e >> 2) + 4 * half) * 32 + col] = tot[q][e];
-  }
+  for (int q = 0; q < PW; ++q)
+    if (wp.own[q]) store_slab(partial + ((chunk * k + j) * npairs + wid + 4 * q) * 1024, tot[q], half, col);
 }
-#undef GMM_LOAD_X
 
 // blockIdx.y = component j < k: partial [nchunk][k][npairs][1024] -> S_j (symmetric fill), 16 threads per element
 // each summing a fixed stride of chunks, then a fixed-order sum.  blockIdx.y == k (one block): the scalars,
@@ -390,7 +320,6 @@ __global__ __launch_bounds__(256) void gmm_reduce_kernel(const double* __restric
                                                          const double* __restrict__ spart, int nblk,
                                                          double* __restrict__ stats) {
   __shared__ double red[16][16];
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
   if ((int)blockIdx.y == (with_S ? k : 0)) {  // without S (PREDICT / EVAL) the grid is this one block
     if (blockIdx.x != 0) return;
     double* red4 = &red[0][0];  // [4][64]
@@ -409,29 +338,10 @@ __global__ __launch_bounds__(256) void gmm_reduce_kernel(const double* __restric
     }
     return;
   }
-  const int j = blockIdx.y;
-  const int64_t idx = (int64_t)blockIdx.x * 16 + el;
-  const bool ok = idx < (int64_t)npairs * 1024;
-  const int gp = ok ? (int)(idx >> 10) : 0, e = ok ? (int)(idx & 1023) : 0;
-  double s = 0.0;
-  if (ok)
-    for (int b = part; b < nchunk; b += 16)
-      s += partial[(((int64_t)b * k + j) * npairs + gp) * 1024 + e];
-  red[part][el] = s;
-  __syncthreads();
-  if (part == 0 && ok) {
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += red[i][el];
-    int I, J;
-    pair_ij(gp, T, I, J);
-    const int a = I * 32 + (e >> 5), b = J * 32 + (e & 31);
-    if (a < D && b < D && !(a == D - 1 && b == D - 1)) {
-      double* Sj = S + (int64_t)j * D * D;
-      Sj[(int64_t)a * D + b] = t;
-      Sj[(int64_t)b * D + a] = t;
-    }
-  }
+  const int64_t j = blockIdx.y;
+  reduce_slabs(red, partial + j * npairs * 1024, (int64_t)k * npairs, nchunk, npairs,
+               [T](int p, int& I, int& J) { pair_ij(p, T, I, J); }, D, S + j * D * D,
+               [D](int a, int b) { return a == D - 1 && b == D - 1; });
 }
 
 struct GmmPlan {
@@ -471,16 +381,7 @@ GmmPlan gmm_plan(int64_t n, int d, int k) {
   return pl;
 }
 
-// dynamic LDS above the 64 KB default (the E-step at k = 32 and d > 96): raised once per kernel and device
-int raise_lds(const void* fn, bool* raised, size_t bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && raised[dev]) return 0;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return (int)e;
-  if (dev >= 0 && dev < 64) raised[dev] = true;
-  return 0;
-}
-
+// the E-step's dynamic LDS passes the 64 KB default at k = 32 and d > 96; the moment kernel's widest plan is 33 KB
 template <int VW>
 int resp_launch(const GmmPlan& pl, const float* X, int64_t n, int d, int64_t ldx, const double* w, const float* cf,
                 const float* AT, const double* corr, const double* logc, int k, int mode, float* sr, double* R,
@@ -539,7 +440,7 @@ CDNA_API int cdna_gmm_step(const float* X, int64_t n, int d, int64_t ldx, const 
   if (mode == kStep && (S == nullptr || ws == nullptr)) return (int)hipErrorInvalidValue;
   if (mode == kPredict && (R == nullptr || assign == nullptr)) return (int)hipErrorInvalidValue;
   const GmmPlan pl = gmm_plan(n, d, k);
-  const bool vec = d % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  const bool vec = float4_rows(X, d, ldx);
   float* sr = ws;
   double* partial = ws != nullptr ? reinterpret_cast<double*>(ws + (n * k + 1) / 2 * 2) : nullptr;
   int rc = vec ? resp_launch<4>(pl, X, n, d, ldx, w, cf, AT, corr, logc, k, mode, sr, R, assign, sws, st)

@@ -20,10 +20,12 @@
 // through an LDS transpose (ds_read of 8 consecutive rows per lane).  The
 // streaming form (gram_bf16s_kernel) reads X once with all tile pairs per
 // block; gram_bf16_kernel remains for unaligned / wide inputs.
-#include "common.h"
+#include "symtile.h"
 #include <cstdlib>
 
 namespace {
+
+using namespace symtile;
 
 constexpr int kMaxPairs = 160;
 struct PairTable {
@@ -101,10 +103,7 @@ __global__ __launch_bounds__(256) void gram_f32_kernel(const float* __restrict__
 #pragma unroll
   for (int p = 0; p < P; ++p)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = (e & 3) + 8 * (e >> 2) + 4 * half;
-      atomicAdd(&red[p * 1024 + row * 32 + col], acc[p][e]);
-    }
+    for (int e = 0; e < 16; ++e) atomicAdd(&red[p * 1024 + acc_row(e, half) * 32 + col], acc[p][e]);
   __syncthreads();
   for (int i = threadIdx.x; i < P * 1024; i += 256) {
     const int p = i >> 10;
@@ -172,10 +171,7 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(const float* __restrict_
 #pragma unroll
   for (int p = 0; p < P; ++p)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = (e & 3) + 8 * (e >> 2) + 4 * half;
-      atomicAdd(&red[p * 1024 + row * 32 + col], acc[p][e]);
-    }
+    for (int e = 0; e < 16; ++e) atomicAdd(&red[p * 1024 + acc_row(e, half) * 32 + col], acc[p][e]);
   __syncthreads();
   for (int i = threadIdx.x; i < P * 1024; i += 256) {
     const int p = i >> 10;
@@ -312,12 +308,8 @@ __global__ __launch_bounds__(256) void gram_bf16s_kernel(const float* __restrict
   }
   const int col = lane & 31;
 #pragma unroll
-  for (int j = 0; j < PW; ++j) {
-    if (pr[j] >= npairs) continue;
-    float* dst = partial + ((int64_t)blockIdx.x * npairs + pr[j]) * 1024;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) dst[((e & 3) + 8 * (e >> 2) + 4 * half) * 32 + col] = acc[j][e];
-  }
+  for (int j = 0; j < PW; ++j)
+    if (pr[j] < npairs) store_slab(partial + ((int64_t)blockIdx.x * npairs + pr[j]) * 1024, acc[j], half, col);
 }
 #undef GRAM_LOAD
 #undef GRAM_STORE
@@ -484,39 +476,16 @@ __global__ __launch_bounds__(256) void gram_bf16d_kernel(const float* __restrict
   __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));        // drain the spare DMA rounds before the block exits
   const int col = lane & 31;
 #pragma unroll
-  for (int j = 0; j < PW; ++j) {
-    if (pr[j] >= npairs) continue;
-    float* dst = partial + ((int64_t)blockIdx.x * npairs + pr[j]) * 1024;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) dst[((q & 3) + 8 * (q >> 2) + 4 * half) * 32 + col] = acc[j][q];
-  }
+  for (int j = 0; j < PW; ++j)
+    if (pr[j] < npairs) store_slab(partial + ((int64_t)blockIdx.x * npairs + pr[j]) * 1024, acc[j], half, col);
 }
 
-// partial [nblk][npairs][1024] -> out (symmetric fill).  16 threads per element each sum a fixed stride of
-// blocks, then a fixed-order LDS tree: deterministic, and 16x the parallelism of one thread per element
-// (the serial 1024-block loop took 0.35 ms of a 3.6 ms fit).
+// partial [nblk][npairs][1024] -> out (symmetric fill), symtile::reduce_slabs with the by-value pair table
 __global__ __launch_bounds__(256) void gram_reduce_kernel(const float* __restrict__ partial, int nblk, int npairs,
                                                           PairTable tab, int D, double* __restrict__ out) {
   __shared__ double red[16][16];
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int64_t idx = (int64_t)blockIdx.x * 16 + el;
-  const bool ok = idx < (int64_t)npairs * 1024;
-  const int gp = ok ? (int)(idx >> 10) : 0, e = ok ? (int)(idx & 1023) : 0;
-  double s = 0.0;
-  if (ok)
-    for (int b = part; b < nblk; b += 16) s += (double)partial[((int64_t)b * npairs + gp) * 1024 + e];
-  red[part][el] = s;
-  __syncthreads();
-  if (part == 0 && ok) {
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += red[q][el];
-    const int i = tab.I[gp] * 32 + (e >> 5), j = tab.J[gp] * 32 + (e & 31);
-    if (i < D && j < D) {
-      out[(int64_t)i * D + j] = t;
-      out[(int64_t)j * D + i] = t;
-    }
-  }
+  reduce_slabs(red, partial, npairs, nblk, npairs, [&tab](int p, int& I, int& J) { I = tab.I[p], J = tab.J[p]; }, D,
+               out, [](int, int) { return false; });
 }
 
 struct GramPlan {
@@ -529,13 +498,13 @@ GramPlan make_plan(int64_t n, int d, bool bf16) {
   GramPlan pl{};
   pl.D = d + 2;
   const int T = (pl.D + 31) / 32;
-  int k = 0;
-  for (int i = 0; i < T; ++i)
-    for (int j = i; j < T; ++j) {
-      pl.tab.I[k] = (int16_t)i;
-      pl.tab.J[k] = (int16_t)j;
-      ++k;
-    }
+  const int k = T * (T + 1) / 2;
+  for (int p = 0; p < k && p < kMaxPairs; ++p) {
+    int I, J;
+    pair_ij(p, T, I, J);
+    pl.tab.I[p] = (int16_t)I;
+    pl.tab.J[p] = (int16_t)J;
+  }
   pl.npairs = k;
   const int maxP = bf16 ? 4 : 8;
   pl.ngroups = (k + maxP - 1) / maxP;
@@ -561,8 +530,7 @@ GramPlan make_plan(int64_t n, int d, bool bf16) {
 constexpr int kStreamMaxD = 160;
 
 bool stream_ok(const float* X, int d, int64_t ldx, const float* shift) {
-  return d % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
-         (reinterpret_cast<uintptr_t>(shift) & 15) == 0 && d + 2 <= kStreamMaxD;
+  return float4_rows(X, d, ldx) && (reinterpret_cast<uintptr_t>(shift) & 15) == 0 && d + 2 <= kStreamMaxD;
 }
 
 GramPlan make_stream_plan(int64_t n, int d) {
@@ -595,21 +563,23 @@ void launch_stream_ni(const GramPlan& pl, const float* X, int64_t n, int d, int6
 }
 
 template <int PW, int CPW>
-void launch_direct(const GramPlan& pl, const float* X, int64_t n, int d, const float* y, const float* shift,
-                   float yshift, float* ws, hipStream_t st) {
+int launch_direct(const GramPlan& pl, const float* X, int64_t n, int d, const float* y, const float* shift,
+                  float yshift, float* ws, hipStream_t st) {
   const int Dpad = ((pl.D + 31) / 32) * 32;
-  const size_t lds = (size_t)kDStages * CPW * kDWaves * 1024 + (size_t)Dpad * (kDRows + 8) * 2;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gram_bf16d_kernel<PW, CPW>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((gram_bf16d_kernel<PW, CPW>), dim3(pl.nblk), dim3(256), lds, st, X, n, d, y, shift, yshift,
+  const auto lds = [](int dpad) { return (size_t)kDStages * CPW * kDWaves * 1024 + (size_t)dpad * (kDRows + 8) * 2; };
+  static bool raised[64] = {};  // the ring passes the 64 KB default: raised to the instantiation's widest plan
+  const int rc = raise_lds(reinterpret_cast<const void*>(gram_bf16d_kernel<PW, CPW>), raised, lds(128));
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL((gram_bf16d_kernel<PW, CPW>), dim3(pl.nblk), dim3(256), lds(Dpad), st, X, n, d, y, shift, yshift,
                      pl.tab, pl.npairs, Dpad, ws, pl.rows_per_unit);
+  return 0;
 }
 
 // direct-to-LDS streaming plan: one resident block per CU, contiguous rows (ldx == d), d % 4 == 0, and the
 // staging ring + bf16 tile within 160 KB (d <= 108: 7 chunk rounds per wave)
 bool direct_ok(const float* X, int d, int64_t ldx, const float* shift) {
-  return ldx == d && d % 4 == 0 && d + 2 <= 128 && (d / 4 + 1 + kDWaves - 1) / kDWaves <= 7 &&
-         (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(shift) & 15) == 0;
+  return ldx == d && float4_rows(X, d, ldx) && (reinterpret_cast<uintptr_t>(shift) & 15) == 0 && d + 2 <= 128 &&
+         (d / 4 + 1 + kDWaves - 1) / kDWaves <= 7;
 }
 
 GramPlan make_direct_plan(int64_t n, int d) {
@@ -627,16 +597,16 @@ GramPlan make_direct_plan(int64_t n, int d) {
 }
 
 template <int PW>
-void launch_direct_cpw(const GramPlan& pl, const float* X, int64_t n, int d, const float* y, const float* shift,
+int launch_direct_cpw(const GramPlan& pl, const float* X, int64_t n, int d, const float* y, const float* shift,
                        float yshift, float* ws, hipStream_t st) {
   switch ((d / 4 + 1 + kDWaves - 1) / kDWaves) {
     case 1:
-    case 2: launch_direct<PW, 2>(pl, X, n, d, y, shift, yshift, ws, st); break;
-    case 3: launch_direct<PW, 3>(pl, X, n, d, y, shift, yshift, ws, st); break;
-    case 4: launch_direct<PW, 4>(pl, X, n, d, y, shift, yshift, ws, st); break;
-    case 5: launch_direct<PW, 5>(pl, X, n, d, y, shift, yshift, ws, st); break;
-    case 6: launch_direct<PW, 6>(pl, X, n, d, y, shift, yshift, ws, st); break;
-    default: launch_direct<PW, 7>(pl, X, n, d, y, shift, yshift, ws, st); break;
+    case 2: return launch_direct<PW, 2>(pl, X, n, d, y, shift, yshift, ws, st);
+    case 3: return launch_direct<PW, 3>(pl, X, n, d, y, shift, yshift, ws, st);
+    case 4: return launch_direct<PW, 4>(pl, X, n, d, y, shift, yshift, ws, st);
+    case 5: return launch_direct<PW, 5>(pl, X, n, d, y, shift, yshift, ws, st);
+    case 6: return launch_direct<PW, 6>(pl, X, n, d, y, shift, yshift, ws, st);
+    default: return launch_direct<PW, 7>(pl, X, n, d, y, shift, yshift, ws, st);
   }
 }
 
@@ -678,12 +648,14 @@ CDNA_API int cdna_gram(const float* X, int64_t n, int d, int64_t ldx, const floa
   if (pl.npairs > kMaxPairs) return (int)hipErrorInvalidValue;
   if (bf16 && direct_ok(X, d, ldx, shift)) {
     pl = make_direct_plan(n, d);
+    int rc = 0;
     switch ((pl.npairs + kDWaves - 1) / kDWaves) {
-      case 1: launch_direct_cpw<1>(pl, X, n, d, y, shift, yshift, ws, st); break;
-      case 2: launch_direct_cpw<2>(pl, X, n, d, y, shift, yshift, ws, st); break;
-      case 3: launch_direct_cpw<3>(pl, X, n, d, y, shift, yshift, ws, st); break;
-      default: launch_direct_cpw<4>(pl, X, n, d, y, shift, yshift, ws, st); break;
+      case 1: rc = launch_direct_cpw<1>(pl, X, n, d, y, shift, yshift, ws, st); break;
+      case 2: rc = launch_direct_cpw<2>(pl, X, n, d, y, shift, yshift, ws, st); break;
+      case 3: rc = launch_direct_cpw<3>(pl, X, n, d, y, shift, yshift, ws, st); break;
+      default: rc = launch_direct_cpw<4>(pl, X, n, d, y, shift, yshift, ws, st); break;
     }
+    if (rc != 0) return rc;
   } else if (bf16 && stream_ok(X, d, ldx, shift)) {
     pl = make_stream_plan(n, d);
     const int pw = (pl.npairs + 3) / 4;  // 4 waves share the tile pairs

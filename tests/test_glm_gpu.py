@@ -3,7 +3,8 @@ end to end on the GPU against the CPU fit.
 
 Shapes are the smallest at which the kernel can go wrong: a single row, the 64-row tile edge with d % 4 != 0 (the
 scalar-load variant), one feature, the benchmark's d = 100, the d + 2 = 128 cap with many blocks and a ragged last
-tile, one past the cap (the composition through K1, no K22 launch), strided rows, zero weights with an offset.
+tile, one past the cap (the composition through K1, no K22 launch), strided rows, zero weights with an offset, a
+65..96-wide Gram (two tile pairs per wave) with either kind of load.
 
 Tolerances: G to rtol 1e-5 and atol 1e-3 sqrt(n) max(W) (test_gram_f32's bound for the exact-fp32 MFMA with fp32
 block accumulation; the weight's factor follows from linearity); the fp64 scalars to rtol 1e-10 (fp64 exp / log
@@ -26,8 +27,10 @@ PAIRS = [("poisson", "log"), ("binomial", "logit"), ("gamma", "inverse")]
 SHAPES = [(1, 4, None, False), (63, 3, None, False), (64, 3, None, False), (65, 3, None, False),
           (200, 1, None, False), (5000, 100, None, False), (70001, 126, None, False), (3000, 127, None, False),
           (9000, 100, 101, False), (4096, 30, None, True),
-          # float4-load variant with two tile pairs per wave, at the widest d % 4 == 0, and with a row stride
-          (4097, 60, None, False), (20000, 124, None, True), (5000, 100, 104, False)]
+          # float4-load variant with 3 tile pairs (one per wave), at the widest d % 4 == 0, and with a row stride
+          (4097, 60, None, False), (20000, 124, None, True), (5000, 100, 104, False),
+          # 65 <= d + 2 <= 96: 6 tile pairs, two per wave; float4 loads and a ragged last tile, then scalar loads
+          (4097, 64, None, False), (1500, 66, None, True)]
 
 
 @functools.lru_cache(maxsize=None)

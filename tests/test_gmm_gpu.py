@@ -3,7 +3,8 @@ module derives from the inputs, and a GaussianMixture fitted end to end on the G
 
 Shapes are the smallest at which the kernels can go wrong: a single row, the 64-row tile edge with d % 4 != 0 (the
 scalar-load variant), one feature, the benchmark's d = 100 and k = 8, many blocks with a ragged last tile, the d and
-k caps, strided rows (one float4-addressable, one not), zero weights.  Every test prints its observed error / bound
+k caps, strided rows (one float4-addressable, one not), zero weights, a 65..96-wide moment matrix (two tile pairs per
+wave) with either kind of load.  Every test prints its observed error / bound
 ratios before it asserts (``-s`` shows them; profiles/r10/gmm.md records a run).
 
 End to end (``test_fit_on_device_matches_cpu``): 20000 x 20, k = 3, both fits on fp32 rows from the same seed.  The
@@ -34,7 +35,9 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(1, 4, 2, None, False), (63, 3, 2, None, False), (64, 3, 2, None, False), (65, 3, 2, None, False),
           (200, 1, 2, None, False), (5000, 100, 8, None, False), (70001, 126, 4, None, False),
           (3000, 127, 3, None, False), (4096, 20, 32, None, False), (9000, 100, 8, 101, False),
-          (5000, 100, 8, 104, False), (4096, 30, 5, None, True)]
+          (5000, 100, 8, 104, False), (4096, 30, 5, None, True),
+          # 65 <= d + 1 <= 96: 6 tile pairs, the moment kernels with two tile pairs per wave (float4 and scalar loads)
+          (4097, 64, 3, None, False), (1500, 66, 2, None, True)]
 
 
 class Counting:
