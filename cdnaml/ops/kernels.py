@@ -25,6 +25,35 @@ from ._base import _TORCH_DT, _native, _ptr, _stream, upload  # noqa: F401
 
 
 # --------------------------------------------------------------------- K1
+def _gram_operands(X: torch.Tensor, shift: Optional[torch.Tensor]):
+    """The fp32 X (unit column stride) and shift tensors whose pointers K1 is called with."""
+    if X.dtype != torch.float32:
+        X = X.float()
+    X = X if X.stride(1) == 1 else X.contiguous()
+    return X, None if shift is None else shift.float().contiguous()
+
+
+GRAM_KERNELS = ("direct", "stream", "tiled", "f32")
+
+
+def gram_plan(X: torch.Tensor, shift: Optional[torch.Tensor] = None, bf16: bool = False) -> Dict[str, object]:
+    """What :func:`gram` runs for these operands, from the dispatch's own host function (nothing is launched):
+    ``kernel`` (one of GRAM_KERNELS, or "host" where gram takes the library GEMM), ``p`` (tile pairs per wave of the
+    direct and stream kernels, per block of the tiled and f32 ones), ``q`` (DMA chunks per wave of the direct kernel,
+    load items per thread of the stream kernel, else 0), ``nblk``, ``ngroups``, ``rows_per_unit`` (rows per block;
+    per wave for f32) and ``npairs``."""
+    n, d = X.shape
+    if X.dtype == torch.float64 or not _native(X) or d + 2 > 512:
+        return {"kernel": "host"}
+    X, sh = _gram_operands(X, shift)
+    out = np.zeros(7, dtype=np.int32)
+    _lib.check(_lib.lib().cdna_gram_plan(_ptr(X), n, d, X.stride(0), _ptr(sh), int(bf16), out.ctypes.data),
+               "cdna_gram_plan")
+    kern, p, q, nblk, ngroups, rpu, npairs = (int(v) for v in out)
+    return {"kernel": GRAM_KERNELS[kern], "p": p, "q": q, "nblk": nblk, "ngroups": ngroups, "rows_per_unit": rpu,
+            "npairs": npairs}
+
+
 def gram(X: torch.Tensor, y: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
          yshift: float = 0.0, bf16: bool = False, fp64: bool = False) -> torch.Tensor:
     """Return A^T A (float64, (d+2)x(d+2)) for A = [X - shift | 1 | y - yshift].
@@ -45,9 +74,8 @@ def gram(X: torch.Tensor, y: Optional[torch.Tensor] = None, shift: Optional[torc
     if X.dtype != torch.float32:
         X = X.float()
     if _native(X) and d + 2 <= 512 and not fp64:
-        X = X if X.stride(1) == 1 else X.contiguous()
+        X, sh = _gram_operands(X, shift)
         y32 = None if y is None else y.float().contiguous()
-        sh = None if shift is None else shift.float().contiguous()
         L = _lib.lib()
         ws_n = L.cdna_gram_workspace(n, d, int(bf16))
         ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=X.device)
@@ -1749,9 +1777,9 @@ def glm_step(X: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], offset
     fp32 X on a GPU with d + 2 <= 128 (any n >= 1, row stride and alignment) runs the fused K22 kernel: one
     launch that reads X once, exact-fp32 MFMA Gram with the augmented row rounded to fp32, partial sums reduced
     in a fixed order: two calls on the same input return the same bits.  Bit-identical reruns of G are part of
-    the contract inside this range only: past the cap G comes from K.gram's fp32 path, whose LDS float atomics
-    fold the waves in no fixed order.  Everything else takes the host formulation, the same formulas as torch
-    fp64 ops: fp64 X entirely in fp64; fp32 X past the cap on a GPU through a scaled copy and
+    the contract inside this range only: past the cap G comes from torch elementwise ops and K.gram's fp32 path
+    (itself bit-identical on reruns, tests/test_gram_gpu.py).  Everything else takes the host formulation, the
+    same formulas as torch fp64 ops: fp64 X entirely in fp64; fp32 X past the cap on a GPU through a scaled copy and
     K.gram(fp64=False).
     """
     n, d = X.shape

@@ -13,8 +13,8 @@
 // i.e. each half-wave reads 128 contiguous bytes of one row: fully coalesced
 // global loads straight into the MFMA operands, no LDS staging needed.
 // Each wave owns a contiguous row range and P upper-triangular tiles; the 4
-// waves of a block are folded through LDS atomics and each block writes one
-// f32 partial slab, reduced deterministically in f64 by gram_reduce_kernel.
+// waves of a block are folded through LDS in wave order and each block writes
+// one f32 partial slab, reduced deterministically in f64 by gram_reduce_kernel.
 //
 // bf16 variant: inputs rounded to bf16 and fed to v_mfma_f32_32x32x16_bf16
 // through an LDS transpose (ds_read of 8 consecutive rows per lane).  The
@@ -48,6 +48,24 @@ __device__ __forceinline__ float col_shift(const float* __restrict__ shift, floa
   return 0.f;
 }
 
+// The block's four waves' accumulators -> red [P][1024], added in wave order with a barrier between waves (wave 0
+// stores, so red needs no clearing): the same bits on every run, which LDS float atomics (arrival order) did not give.
+template <int P>
+__device__ __forceinline__ void fold_waves(float* red, const f32x16 (&acc)[P], int wid, int half, int col) {
+  for (int w = 0; w < 4; ++w) {
+    if (wid == w) {
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          float* r = &red[p * 1024 + acc_row(e, half) * 32 + col];
+          *r = w == 0 ? acc[p][e] : *r + acc[p][e];
+        }
+    }
+    __syncthreads();
+  }
+}
+
 template <int P>
 __global__ __launch_bounds__(256) void gram_f32_kernel(const float* __restrict__ X, int64_t n, int d, int64_t ldx,
                                                        const float* __restrict__ y, const float* __restrict__ shift,
@@ -56,7 +74,6 @@ __global__ __launch_bounds__(256) void gram_f32_kernel(const float* __restrict__
   __shared__ float red[P * 1024];
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < P * 1024; i += 256) red[i] = 0.f;
 
   const int pbase = blockIdx.y * P;
   int ca[P], cb[P];
@@ -98,13 +115,7 @@ __global__ __launch_bounds__(256) void gram_f32_kernel(const float* __restrict__
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[p], b1[p], acc[p], 0, 0, 0);
     }
   }
-  __syncthreads();
-  const int col = lane & 31;
-#pragma unroll
-  for (int p = 0; p < P; ++p)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) atomicAdd(&red[p * 1024 + acc_row(e, half) * 32 + col], acc[p][e]);
-  __syncthreads();
+  fold_waves<P>(red, acc, wid, half, lane & 31);
   for (int i = threadIdx.x; i < P * 1024; i += 256) {
     const int p = i >> 10;
     if (pbase + p < npairs) partial[((int64_t)blockIdx.x * npairs + pbase + p) * 1024 + (i & 1023)] = red[i];
@@ -127,7 +138,6 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(const float* __restrict_
   float* red = reinterpret_cast<float*>(smem + (size_t)Dpad * kColStride * 2);
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < P * 1024; i += 256) red[i] = 0.f;
   const int pbase = blockIdx.y * P;
   int ta[P], tb[P];
 #pragma unroll
@@ -166,13 +176,7 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(const float* __restrict_
       acc[p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[p], 0, 0, 0);
     }
   }
-  __syncthreads();
-  const int col = lane & 31;
-#pragma unroll
-  for (int p = 0; p < P; ++p)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) atomicAdd(&red[p * 1024 + acc_row(e, half) * 32 + col], acc[p][e]);
-  __syncthreads();
+  fold_waves<P>(red, acc, wid, half, lane & 31);
   for (int i = threadIdx.x; i < P * 1024; i += 256) {
     const int p = i >> 10;
     if (pbase + p < npairs) partial[((int64_t)blockIdx.x * npairs + pbase + p) * 1024 + (i & 1023)] = red[i];
@@ -555,9 +559,8 @@ void launch_stream(const GramPlan& pl, const float* X, int64_t n, int d, int64_t
 }
 
 template <int PW>
-void launch_stream_ni(const GramPlan& pl, const float* X, int64_t n, int d, int64_t ldx, const float* y,
+void launch_stream_ni(const GramPlan& pl, int ni, const float* X, int64_t n, int d, int64_t ldx, const float* y,
                       const float* shift, float yshift, float* ws, hipStream_t st) {
-  const int ni = (8 * (d / 4) + 255) / 256;
   if (ni <= 1) launch_stream<PW, 1>(pl, X, n, d, ldx, y, shift, yshift, ws, st);
   else launch_stream<PW, 2>(pl, X, n, d, ldx, y, shift, yshift, ws, st);
 }
@@ -597,10 +600,9 @@ GramPlan make_direct_plan(int64_t n, int d) {
 }
 
 template <int PW>
-int launch_direct_cpw(const GramPlan& pl, const float* X, int64_t n, int d, const float* y, const float* shift,
-                       float yshift, float* ws, hipStream_t st) {
-  switch ((d / 4 + 1 + kDWaves - 1) / kDWaves) {
-    case 1:
+int launch_direct_cpw(const GramPlan& pl, int cpw, const float* X, int64_t n, int d, const float* y,
+                       const float* shift, float yshift, float* ws, hipStream_t st) {
+  switch (cpw) {
     case 2: return launch_direct<PW, 2>(pl, X, n, d, y, shift, yshift, ws, st);
     case 3: return launch_direct<PW, 3>(pl, X, n, d, y, shift, yshift, ws, st);
     case 4: return launch_direct<PW, 4>(pl, X, n, d, y, shift, yshift, ws, st);
@@ -625,6 +627,42 @@ void launch_bf16(const GramPlan& pl, const float* X, int64_t n, int d, int64_t l
                      yshift, pl.tab, pl.npairs, Dpad, ws, pl.rows_per_unit);
 }
 
+// The kernel and template instantiation of one call, decided on the host from the call's shape and pointers alone
+// (cdna_gram dispatches on it, cdna_gram_plan reports it).  a: PW (direct, stream) or P (tiled, f32); b: CPW
+// (direct), NI (stream), 0 otherwise.
+enum { kKernDirect = 0, kKernStream = 1, kKernTiled = 2, kKernF32 = 3 };
+struct GramChoice {
+  GramPlan pl;
+  int kern, a, b;
+};
+
+int direct_cpw(int d) {
+  const int c = (d / 4 + 1 + kDWaves - 1) / kDWaves;
+  return c < 2 ? 2 : c;
+}
+
+int choose(const float* X, int64_t n, int d, int64_t ldx, const float* shift, bool bf16, GramChoice& c) {
+  if (d + 2 > 32 * 17) return (int)hipErrorInvalidValue;
+  c.pl = make_plan(n, d, bf16);
+  if (c.pl.npairs > kMaxPairs) return (int)hipErrorInvalidValue;
+  if (bf16 && direct_ok(X, d, ldx, shift)) {
+    c.pl = make_direct_plan(n, d);
+    c.kern = kKernDirect;
+    c.a = (c.pl.npairs + kDWaves - 1) / kDWaves;
+    c.b = direct_cpw(d);
+  } else if (bf16 && stream_ok(X, d, ldx, shift)) {
+    c.pl = make_stream_plan(n, d);
+    c.kern = kKernStream;
+    c.a = (c.pl.npairs + 3) / 4;  // 4 waves share the tile pairs
+    c.b = (8 * (d / 4) + 255) / 256 <= 1 ? 1 : 2;
+  } else {
+    c.kern = bf16 ? kKernTiled : kKernF32;
+    c.a = c.pl.P;
+    c.b = 0;
+  }
+  return 0;
+}
+
 }  // namespace
 
 // Workspace (in floats) needed by cdna_gram for an n×d problem.
@@ -643,37 +681,35 @@ CDNA_API int64_t cdna_gram_workspace(int64_t n, int d, int bf16) {
 // d+1 is y (zeros if y == nullptr).  Supports d+2 <= 512 (160 tile pairs).
 CDNA_API int cdna_gram(const float* X, int64_t n, int d, int64_t ldx, const float* y, const float* shift, float yshift,
                        double* out, float* ws, int bf16, hipStream_t st) {
-  if (d + 2 > 32 * 17) return (int)hipErrorInvalidValue;
-  GramPlan pl = make_plan(n, d, bf16 != 0);
-  if (pl.npairs > kMaxPairs) return (int)hipErrorInvalidValue;
-  if (bf16 && direct_ok(X, d, ldx, shift)) {
-    pl = make_direct_plan(n, d);
+  GramChoice c{};
+  const int bad = choose(X, n, d, ldx, shift, bf16 != 0, c);
+  if (bad != 0) return bad;
+  const GramPlan& pl = c.pl;
+  if (c.kern == kKernDirect) {
     int rc = 0;
-    switch ((pl.npairs + kDWaves - 1) / kDWaves) {
-      case 1: rc = launch_direct_cpw<1>(pl, X, n, d, y, shift, yshift, ws, st); break;
-      case 2: rc = launch_direct_cpw<2>(pl, X, n, d, y, shift, yshift, ws, st); break;
-      case 3: rc = launch_direct_cpw<3>(pl, X, n, d, y, shift, yshift, ws, st); break;
-      default: rc = launch_direct_cpw<4>(pl, X, n, d, y, shift, yshift, ws, st); break;
+    switch (c.a) {
+      case 1: rc = launch_direct_cpw<1>(pl, c.b, X, n, d, y, shift, yshift, ws, st); break;
+      case 2: rc = launch_direct_cpw<2>(pl, c.b, X, n, d, y, shift, yshift, ws, st); break;
+      case 3: rc = launch_direct_cpw<3>(pl, c.b, X, n, d, y, shift, yshift, ws, st); break;
+      default: rc = launch_direct_cpw<4>(pl, c.b, X, n, d, y, shift, yshift, ws, st); break;
     }
     if (rc != 0) return rc;
-  } else if (bf16 && stream_ok(X, d, ldx, shift)) {
-    pl = make_stream_plan(n, d);
-    const int pw = (pl.npairs + 3) / 4;  // 4 waves share the tile pairs
-    switch (pw) {
-      case 1: launch_stream_ni<1>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
-      case 2: launch_stream_ni<2>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
-      case 3: launch_stream_ni<3>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
-      default: launch_stream_ni<4>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
+  } else if (c.kern == kKernStream) {
+    switch (c.a) {
+      case 1: launch_stream_ni<1>(pl, c.b, X, n, d, ldx, y, shift, yshift, ws, st); break;
+      case 2: launch_stream_ni<2>(pl, c.b, X, n, d, ldx, y, shift, yshift, ws, st); break;
+      case 3: launch_stream_ni<3>(pl, c.b, X, n, d, ldx, y, shift, yshift, ws, st); break;
+      default: launch_stream_ni<4>(pl, c.b, X, n, d, ldx, y, shift, yshift, ws, st); break;
     }
-  } else if (bf16) {
-    switch (pl.P) {
+  } else if (c.kern == kKernTiled) {
+    switch (c.a) {
       case 1: launch_bf16<1>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
       case 2: launch_bf16<2>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
       case 3: launch_bf16<3>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
       default: launch_bf16<4>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
     }
   } else {
-    switch (pl.P) {
+    switch (c.a) {
       case 1: launch_f32<1>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
       case 2: launch_f32<2>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
       case 3: launch_f32<3>(pl, X, n, d, ldx, y, shift, yshift, ws, st); break;
@@ -690,4 +726,21 @@ CDNA_API int cdna_gram(const float* X, int64_t n, int d, int64_t ldx, const floa
   hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)((tot + 15) / 16)), dim3(256), 0, st, ws, pl.nblk,
                      pl.npairs, pl.tab, pl.D, out);
   return (int)hipGetLastError();
+}
+
+// What cdna_gram would run for this call, without launching anything: out[7] = {kernel (0 direct, 1 stream, 2 tiled
+// bf16, 3 f32), PW or P, CPW (direct) / NI (stream) / 0, blocks, pair groups, rows per block (per wave: f32), tile
+// pairs}.  X and shift are only looked at as addresses (their alignment picks the kernel).
+CDNA_API int cdna_gram_plan(const float* X, int64_t n, int d, int64_t ldx, const float* shift, int bf16, int* out) {
+  GramChoice c{};
+  const int bad = choose(X, n, d, ldx, shift, bf16 != 0, c);
+  if (bad != 0) return bad;
+  out[0] = c.kern;
+  out[1] = c.a;
+  out[2] = c.b;
+  out[3] = c.pl.nblk;
+  out[4] = c.pl.ngroups;
+  out[5] = (int)c.pl.rows_per_unit;
+  out[6] = c.pl.npairs;
+  return 0;
 }

@@ -86,7 +86,7 @@ def device_step(dev, n, d, ldx, degenerate, fam, link, mode):
         G2, st2 = K.glm_step(Xd, g(y), g(w), g(off), g(beta), b0, g(shift), zs, fam, link, 0.0, 0.0, mode)
     finally:
         _lib.check = orig
-    if d <= K.GLM_MAX_D:    # K22 has no float atomics: the same bits twice (K1's fp32 path folds waves by LDS atomics)
+    if d <= K.GLM_MAX_D:    # K22 has no float atomics: the same bits twice (past the cap: a composition of torch ops and K1)
         assert torch.equal(G, G2)
     assert torch.equal(st, st2)
     return G.cpu(), st.cpu(), calls
