@@ -9,7 +9,6 @@ kernel alone with HIP events, reporting ms and lane-updates/s.
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -92,64 +91,38 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     n, d, B = int(args.rows), args.d, args.B
-    configs = [
-        # (name, T, L, masked, weights, version, lane map, lds bytes)
-        ("L0 T20 masked w v4", 20, 1, True, True, 4, 2, 65536),
+    # (name, T, L, masked, weights, version, lane map | trees per group, lds bytes): one row per kernel and level
+    # shape.  version 4: node ids (lane map 2 = hist4_kernel, 5 = hist4f_kernel); 6: row codes, unpacked
+    # (hist5_kernel); 7: packed (hist5p, 512-thread blocks up to 64 KB of cells, 1024-thread above); 8: packed and
+    # wave-compacted (hist5q).  "sub": only one child of each sibling pair is built.
+    configs = []
+    for lvl in (0, 2, 4):
+        for ver, tag in ((7, "pk8"), (8, "pkq")):
+            configs.append((f"L{lvl} T20 sub    codes {tag} 128K", 20, 1 << lvl, False, True, ver, 8, 131072))
+    configs += [
+        ("L4 T20 sub msk codes pk8 128K", 20, 16, True, True, 7, 8, 131072),
+        ("L4 T20 sub msk codes pkq 128K", 20, 16, True, True, 8, 8, 131072),
+        ("L7 T1  sub    codes pk8 128K B256", 1, 128, False, True, 7, 8, 131072),
+        ("L7 T1  sub    codes pkq 128K B256", 1, 128, False, True, 8, 8, 131072),
+        ("L0 T20 full   codes pk8 128K", 20, 1, False, True, 7, 8, 131072),
+        ("L4 T20 full   codes pk8 128K", 20, 16, False, True, 7, 8, 131072),
+        # the only row that reaches the packed NT = 16 instantiations (HIST5_PACKED_MAXT is 8 by default)
+        ("L4 T20 full   codes pk16 128K", 20, 16, False, True, 7, 16, 131072),
+        ("L4 T20 masked codes pk8 128K", 20, 16, True, True, 7, 8, 131072),
+        ("L0 T20 full   codes pk8", 20, 1, False, True, 7, 8, 65536),
+        ("L4 T20 full   codes pk8", 20, 16, False, True, 7, 8, 65536),
+        ("L4 T20 masked codes pk8", 20, 16, True, True, 7, 8, 65536),
+        ("L0 T20 full   codes", 20, 1, False, True, 6, 0, 65536),
+        ("L4 T20 full   codes", 20, 16, False, True, 6, 0, 65536),
+        ("L4 T20 masked codes", 20, 16, True, True, 6, 0, 65536),
         ("L0 T20 full   w v4 fast", 20, 1, False, True, 4, 5, 65536),
-        ("L1 T20 full   w v4 fast", 20, 2, False, True, 4, 5, 65536),
         ("L4 T20 full   w v4 fast", 20, 16, False, True, 4, 5, 65536),
         ("L0 T20 masked w v4 fast", 20, 1, True, True, 4, 5, 65536),
         ("L4 T20 masked w v4 fast", 20, 16, True, True, 4, 5, 65536),
-        ("L4 T20 full   w v4 fast 96K", 20, 16, False, True, 4, 5, 98304),
-        ("L0 T20 full   w v5 packed", 20, 1, False, True, 5, 4, 65536),
-        ("L4 T20 full   w v5 packed", 20, 16, False, True, 5, 4, 65536),
-        ("L0 T20 masked w v5 packed", 20, 1, True, True, 5, 4, 65536),
-        ("L4 T20 masked w v5 packed", 20, 16, True, True, 5, 4, 65536),
-        ("L0 T20 masked w v4 rot", 20, 1, True, True, 4, 4, 65536),
-        ("L0 T20 full   w v4 rot", 20, 1, False, True, 4, 4, 65536),
-        ("L4 T20 masked w v4 rot", 20, 16, True, True, 4, 4, 65536),
-        ("L4 T20 full   w v4 rot", 20, 16, False, True, 4, 4, 65536),
-        ("L0 T20 masked w v4 m3", 20, 1, True, True, 4, 3, 65536),
-        ("L0 T20 full   w v4", 20, 1, False, True, 4, 2, 65536),
-        ("L0 T20 full   w v4 m3", 20, 1, False, True, 4, 3, 65536),
+        ("L0 T20 masked w v4", 20, 1, True, True, 4, 2, 65536),
         ("L4 T20 masked w v4", 20, 16, True, True, 4, 2, 65536),
-        ("L4 T20 masked w v4 m3", 20, 16, True, True, 4, 3, 65536),
-        ("L4 T20 masked w v4 40K", 20, 16, True, True, 4, 2, 40960),
-        ("L4 T20 masked w v4 128K", 20, 16, True, True, 4, 2, 131072),
         ("L4 T20 full   w v4", 20, 16, False, True, 4, 2, 65536),
-        ("L0 T20 masked w v2", 20, 1, True, True, 2, 2, 65536),
-        ("L4 T20 masked w v2", 20, 16, True, True, 2, 2, 65536),
     ]
-    if args.variants != "all":
-        configs = [c for c in configs if any(v in c[0] for v in args.variants.split(","))]
-    sub_cfgs = []
-    for lvl in range(5):
-        for ver, tag in ((7, "pk8"), (8, "pkq")):
-            sub_cfgs.append((f"L{lvl} T20 sub    codes {tag} 128K", 20, 1 << lvl, False, True, ver, 8, 131072))
-    sub_cfgs.append(("L4 T20 sub msk codes pk8 128K", 20, 16, True, True, 7, 8, 131072))
-    sub_cfgs.append(("L4 T20 sub msk codes pkq 128K", 20, 16, True, True, 8, 8, 131072))
-    sub_cfgs.append(("L7 T1  sub    codes pk8 128K B256", 1, 128, False, True, 7, 8, 131072))
-    sub_cfgs.append(("L7 T1  sub    codes pkq 128K B256", 1, 128, False, True, 8, 8, 131072))
-    configs = sub_cfgs + [("L2 T20 full   codes pk8 128K", 20, 4, False, True, 7, 8, 131072),
-               ("L3 T20 full   codes pk8 128K", 20, 8, False, True, 7, 8, 131072),
-               ("L1 T20 full   codes pk8 128K", 20, 2, False, True, 7, 8, 131072),
-               ("L4 T20 full   codes pk8 128K", 20, 16, False, True, 7, 8, 131072),
-               ("L0 T20 full   codes pk8 128K", 20, 1, False, True, 7, 8, 131072),
-               ("L4 T20 full   codes pk16 128K", 20, 16, False, True, 7, 16, 131072),
-               ("L4 T20 masked codes pk8 128K", 20, 16, True, True, 7, 8, 131072),
-               ("L0 T20 full   codes pk4", 20, 1, False, True, 7, 4, 65536),
-               ("L4 T20 full   codes pk4", 20, 16, False, True, 7, 4, 65536),
-               ("L0 T20 full   codes pk8 48K", 20, 1, False, True, 7, 8, 49152),
-               ("L0 T20 full   codes pk8", 20, 1, False, True, 7, 8, 65536),
-               ("L0 T20 full   codes pk16", 20, 1, False, True, 7, 16, 65536),
-               ("L1 T20 full   codes pk8", 20, 2, False, True, 7, 8, 65536),
-               ("L4 T20 full   codes pk8", 20, 16, False, True, 7, 8, 65536),
-               ("L4 T20 masked codes pk8", 20, 16, True, True, 7, 8, 65536),
-               ("L0 T20 full   codes", 20, 1, False, True, 6, 0, 65536),
-               ("L1 T20 full   codes", 20, 2, False, True, 6, 0, 65536),
-               ("L4 T20 full   codes", 20, 16, False, True, 6, 0, 65536),
-               ("L0 T20 masked codes", 20, 1, True, True, 6, 0, 65536),
-               ("L4 T20 masked codes", 20, 16, True, True, 6, 0, 65536)] + configs
     if args.variants != "all":
         configs = [c for c in configs if any(v in c[0] for v in args.variants.split(","))]
     for name, T, L, masked, wts, ver, lmap, lds in configs:

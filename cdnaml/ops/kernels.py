@@ -592,8 +592,9 @@ def _prefetched(t: torch.Tensor, absval: bool) -> Optional[float]:
 
 
 def packed_scale_global(v: torch.Tensor, comm) -> float:
-    """``_packed_scale`` from the max |v| over all ranks: every rank quantises identically, so integer
-    histograms all-reduce to the same sums whatever the number of GPUs."""
+    """Power-of-two scale with |round(v * s)| <= 2^23 (packed count|sum LDS words), from the max |v| over all
+    ranks of ``comm`` (None: this one): every rank quantises identically, so integer histograms all-reduce to the
+    same sums whatever the number of GPUs."""
     m = _prefetched(v, True) if v.numel() else 0.0
     if m is None:
         m = _absmax(v)
@@ -607,70 +608,134 @@ def packed_scale_global(v: torch.Tensor, comm) -> float:
 
 
 def _packed_scale(v: torch.Tensor) -> float:
-    """Power-of-two scale with |round(v * s)| <= 2^23 (packed count|sum LDS words)."""
-    m = _absmax(v) if v.numel() else 0.0
-    if not math.isfinite(m):
-        raise ValueError("histogram statistic contains NaN/Inf")
-    if m == 0.0:
-        return 1.0
-    e = math.floor(math.log2((2 ** 23) / m))
-    return float(2.0 ** max(-120, min(100, e)))
+    """``packed_scale_global`` on this rank alone.  Like it, reads a max |v| that ``prefetch_max`` attached to ``v``
+    instead of reducing again (the same value as long as ``v`` has not been written since)."""
+    return packed_scale_global(v, None)
 
 
-def _hist2(mode: int, bins, d, node, weight, v0, v1, label, C, build_slot, slot_tree, id_tree, feat_mask, B,
-           lds_budget, out):
-    """Launch the LDS integer histogram kernel (hist4.hip)."""
-    S = len(slot_tree)
-    G, n, _ = bins.shape
-    T = node.shape[0]
-    kbits = mode | (4 if (mode == 0 and v0 is not None) else 0)
-    per_slot = 8 * B * int(_lib.lib().cdna_hist4_bytes_per_bin(kbits, int(C)))
-    SB = max(1, min(S, lds_budget // per_slot))
-    if per_slot > 150 * 1024:
-        raise ValueError("histogram too large for LDS (classes x bins)")
+def slot_groups(slot_tree, id_tree, SB: int, max_trees: Optional[int] = None) -> list:
+    """The slot groups of a level histogram launch, one per pass of a block over the rows: rows
+    ``(s0, t0, t1, i0, i1)`` = first slot, first and last tree of the group's (at most ``SB``) slots, and the
+    range of active ids of those trees.  ``slot_tree`` / ``id_tree``: the tree of every build slot / active id,
+    ascending.  ``max_trees`` caps the trees of a group (the row-code kernels prefetch one code per tree)."""
     slot_tree = np.asarray(slot_tree)
     id_tree = np.asarray(id_tree)
+    S = len(slot_tree)
     rows = []
-    for a in range(0, S, SB):
+    a = 0
+    while a < S:
         b = min(S, a + SB)
-        t0, t1 = int(slot_tree[a]), int(slot_tree[b - 1])
+        t0 = int(slot_tree[a])
+        if max_trees is not None:
+            b = min(b, int(np.searchsorted(slot_tree, t0 + max_trees, side="left")))
+        t1 = int(slot_tree[b - 1])
         i0 = int(np.searchsorted(id_tree, t0, side="left"))
         i1 = int(np.searchsorted(id_tree, t1, side="right"))
         rows.append((a, t0, t1, i0, i1))
-    grp = torch.tensor(rows, dtype=torch.int32, device=bins.device).reshape(-1)
+        a = b
+    return rows
+
+
+HIST5_NT_BUCKETS = (1, 2, 4, 8, 16)  # trees per group the row-code kernels are instantiated for (histblock.h)
+
+
+def _nt_bucket(nt: int) -> int:
+    return next(b for b in HIST5_NT_BUCKETS if nt <= b)
+
+
+def _hist_per_slot(kbits: int, C: int, B: int) -> int:
+    """LDS bytes of one slot's [8][B] block over all planes."""
+    per_slot = 8 * B * int(_lib.lib().cdna_hist4_bytes_per_bin(kbits, int(C)))
+    if per_slot > 150 * 1024:
+        raise ValueError("histogram too large for LDS (classes x bins)")
+    return per_slot
+
+
+def _hist_launch(name: str, kbits: int, bins, d, T, rows_of, v0, v1, label, C, build_slot, feat_mask, S, B, SB,
+                 rows, target, table, scales, tail, out):
+    """The common tail of the two level-histogram wrappers: chunk count, operand casts, the int64 launch of
+    ``cdna_<name>`` and the un-scaling into ``out``.  ``rows_of``: the kernel's two row-state pointers (node ids
+    and weights, or codes and tfirst); ``table``: its table-size argument; ``scales(v0, v1)`` -> (qs0, qs1) from
+    the cast operands; ``tail``: arguments between qs1 and the output."""
+    G, n, _ = bins.shape
     ng = len(rows)
-    span = max(r[4] - r[3] for r in rows)
-    lds_left = 150 * 1024 - ((SB * per_slot + 15) // 16) * 16 - SB - 16
-    id_span_max = int(min(span, max(0, lds_left // 4), 16384))
-    # 2 x 512-thread blocks per CU when LDS allows; enough chunks to fill 256 CUs
-    target = 1024
+    grp, = upload(bins.device, np.asarray(rows, dtype=np.int32).reshape(-1))
+    # enough chunks to fill 256 CUs; u32 LDS counts: rows/chunk * 255 < 2^32
     nchunk = int(max(1, min((target + G * ng - 1) // (G * ng), (n + 8191) // 8192)))
-    nchunk = max(nchunk, -(-n // (1 << 23)))  # u32 LDS counts: rows/chunk * 255 < 2^32
+    nchunk = max(nchunk, -(-n // (1 << 23)))
     mw = 0 if feat_mask is None else feat_mask.shape[1]
     fm = None if feat_mask is None else feat_mask.int().contiguous()
-    node = node.int().contiguous()
-    weight = None if weight is None else weight.to(torch.uint8).contiguous()
     v0 = None if v0 is None else v0.float().contiguous()
     v1 = None if v1 is None else v1.float().contiguous()
     label = None if label is None else label.int().contiguous()
-    build_slot = build_slot.int().contiguous()
-    vmode = 0
-    if HIST_MAP == 5 and v0 is None and id_span_max >= span:
-        vmode = 32  # fast rotated kernel (LDS slot table must hold the whole id span)
-    wmax = 255 if weight is not None else 1
-    qs0 = _fixed_scale(v0, n, wmax)
-    qs1 = _fixed_scale(v1, n, wmax, qmax_bits=30 if vmode == 32 else 62)
+    bs = build_slot.int().contiguous()
+    qs0, qs1 = scales(v0, v1)
     iout = torch.zeros(out.shape, dtype=torch.int64, device=bins.device)
-    _lib.check(_lib.lib().cdna_hist4(kbits | vmode, _ptr(bins), n, d, T, _ptr(node), _ptr(weight), _ptr(v0),
-                                     _ptr(v1), _ptr(label), int(C), _ptr(build_slot), _ptr(fm), mw, S, B, SB,
-                                     _ptr(grp), ng, nchunk, id_span_max, qs0, qs1, _ptr(iout),
-                                     _stream(bins.device)), "cdna_hist4")
+    _lib.check(getattr(_lib.lib(), "cdna_" + name)(
+        kbits, _ptr(bins), n, d, T, *rows_of, _ptr(v0), _ptr(v1), _ptr(label), int(C), _ptr(bs), _ptr(fm), mw, S, B,
+        SB, _ptr(grp), ng, nchunk, table, qs0, qs1, *tail, _ptr(iout), _stream(bins.device)), "cdna_" + name)
     out.copy_(iout)
-    if mode == 0:
+    if not kbits & 1:
         if v0 is not None:
             out[..., 0] /= qs0
         out[..., 1] /= qs1
     return out
+
+
+def _hist2(mode: int, bins, d, node, weight, v0, v1, label, C, build_slot, slot_tree, id_tree, feat_mask, B,
+           lds_budget, out):
+    """Launch the LDS integer histogram kernel on node ids (hist4.hip)."""
+    S = len(slot_tree)
+    n = bins.shape[1]
+    kbits = mode | (4 if (mode == 0 and v0 is not None) else 0)
+    per_slot = _hist_per_slot(kbits, C, B)
+    SB = max(1, min(S, lds_budget // per_slot))
+    rows = slot_groups(slot_tree, id_tree, SB)
+    span = max(r[4] - r[3] for r in rows)
+    lds_left = 150 * 1024 - ((SB * per_slot + 15) // 16) * 16 - SB - 16
+    id_span_max = int(min(span, max(0, lds_left // 4), 16384))
+    # fast rotated kernel: its LDS slot table must hold the whole id span
+    vmode = 32 if HIST_MAP == 5 and v0 is None and id_span_max >= span else 0
+    wmax = 255 if weight is not None else 1
+    node = node.int().contiguous()
+    weight = None if weight is None else weight.to(torch.uint8).contiguous()
+
+    def scales(v0, v1):
+        return _fixed_scale(v0, n, wmax), _fixed_scale(v1, n, wmax, qmax_bits=30 if vmode == 32 else 62)
+    # 2 x 512-thread blocks per CU when LDS allows
+    return _hist_launch("hist4", kbits | vmode, bins, d, node.shape[0], (_ptr(node), _ptr(weight)), v0, v1, label,
+                        C, build_slot, feat_mask, S, B, SB, rows, 1024, id_span_max, scales, (), out)
+
+
+def _hist_host(bins, d, node, weight, build_slot, feat_mask, B, row_ok, stride, offset, addends, flat) -> None:
+    """Host formulation of the level histograms: every (tree, row) whose node maps to a build slot adds, for each
+    enabled feature f, ``w * addends[k]`` (None: 1) to ``flat[cell * stride + offset, k]``, cell = (slot, f, bin)."""
+    bm = bins_to_matrix(bins, d)
+    n = bm.shape[0]
+    fr = torch.arange(d)
+    bs = build_slot.long()
+    for t in range(node.shape[0]):
+        ids = node[t].long()
+        ok = ids >= 0
+        slot = torch.full_like(ids, -1)
+        slot[ok] = bs[ids[ok]]
+        w = torch.ones(n, dtype=torch.float64) if weight is None else weight[t].double()
+        ok = (slot >= 0) & (w != 0)
+        if row_ok is not None:
+            ok = ok & row_ok
+        if not ok.any():
+            continue
+        rs = slot[ok]
+        idx = (rs[:, None] * d + fr[None, :]) * B + bm[ok]
+        if offset is not None:
+            idx = idx * stride + offset[ok][:, None]
+        msk = torch.ones_like(idx, dtype=torch.bool)
+        if feat_mask is not None:
+            words = feat_mask.long()[rs]  # [m, MW]
+            msk = ((words[:, fr // 32] >> (fr % 32)) & 1).bool()
+        for k, a in enumerate(addends):
+            wx = (w[ok] if a is None else w[ok] * a[ok])[:, None].expand_as(idx)
+            flat[:, k] += torch.bincount(idx[msk], weights=wx[msk], minlength=flat.shape[0])
 
 
 def hist_moments(bins: torch.Tensor, d: int, node: torch.Tensor, weight: Optional[torch.Tensor],
@@ -684,8 +749,7 @@ def hist_moments(bins: torch.Tensor, d: int, node: torch.Tensor, weight: Optiona
     restricted to features enabled in feat_mask[s] (bit f).
     """
     S = len(slot_tree)
-    G, n, _ = bins.shape
-    T = node.shape[0]
+    n = bins.shape[1]
     out = torch.zeros((S, d, B, 2), dtype=torch.float64, device=bins.device)
     if S == 0 or n == 0:
         return out
@@ -693,32 +757,8 @@ def hist_moments(bins: torch.Tensor, d: int, node: torch.Tensor, weight: Optiona
         assert id_tree is not None, "the GPU node-id histograms need id_tree (the tree of every active node)"
         return _hist2(0, bins, d, node, weight, v0, v1, None, 0, build_slot, slot_tree, id_tree, feat_mask, B,
                       lds_budget or HIST_LDS_BUDGET, out)
-    bm = bins_to_matrix(bins, d)
-    a0 = torch.ones(n, dtype=torch.float64) if v0 is None else v0.double()
-    a1 = v1.double()
-    fr = torch.arange(d)
-    flat = out.view(-1, 2)
-    for t in range(T):
-        ids = node[t].long()
-        ok = ids >= 0
-        slot = torch.full_like(ids, -1)
-        slot[ok] = build_slot.long()[ids[ok]]
-        ok = slot >= 0
-        w = torch.ones(n, dtype=torch.float64) if weight is None else weight[t].double()
-        ok = ok & (w != 0)
-        if not ok.any():
-            continue
-        rs = slot[ok]
-        idx = (rs[:, None] * d + fr[None, :]) * B + bm[ok]
-        msk = torch.ones_like(idx, dtype=torch.bool)
-        if feat_mask is not None:
-            words = feat_mask.long()[rs]  # [m, MW]
-            bits = (words[:, fr // 32] >> (fr % 32)) & 1
-            msk = bits.bool()
-        wx0 = (w[ok] * a0[ok])[:, None].expand_as(idx)
-        wx1 = (w[ok] * a1[ok])[:, None].expand_as(idx)
-        flat[:, 0] += torch.bincount(idx[msk], weights=wx0[msk], minlength=flat.shape[0])
-        flat[:, 1] += torch.bincount(idx[msk], weights=wx1[msk], minlength=flat.shape[0])
+    _hist_host(bins, d, node, weight, build_slot, feat_mask, B, None, 1, None,
+               (None if v0 is None else v0.double(), v1.double()), out.view(-1, 2))
     return out
 
 
@@ -728,8 +768,7 @@ def hist_classes(bins: torch.Tensor, d: int, node: torch.Tensor, weight: Optiona
                  id_tree: Optional[np.ndarray] = None) -> torch.Tensor:
     """Per-slot (feature, bin) weighted class counts: out[S, d, B, C] (float64)."""
     S = len(slot_tree)
-    G, n, _ = bins.shape
-    T = node.shape[0]
+    n = bins.shape[1]
     out = torch.zeros((S, d, B, C), dtype=torch.float64, device=bins.device)
     if S == 0 or n == 0:
         return out
@@ -737,27 +776,9 @@ def hist_classes(bins: torch.Tensor, d: int, node: torch.Tensor, weight: Optiona
         assert id_tree is not None, "the GPU node-id histograms need id_tree (the tree of every active node)"
         return _hist2(1, bins, d, node, weight, None, None, label, C, build_slot, slot_tree, id_tree, feat_mask, B,
                       lds_budget or HIST_LDS_BUDGET, out)
-    bm = bins_to_matrix(bins, d)
     lab = label.long()
-    fr = torch.arange(d)
-    flat = out.view(-1)
-    for t in range(T):
-        ids = node[t].long()
-        ok = ids >= 0
-        slot = torch.full_like(ids, -1)
-        slot[ok] = build_slot.long()[ids[ok]]
-        w = torch.ones(n, dtype=torch.float64) if weight is None else weight[t].double()
-        ok = (slot >= 0) & (w != 0) & (lab >= 0) & (lab < C)
-        if not ok.any():
-            continue
-        rs = slot[ok]
-        idx = ((rs[:, None] * d + fr[None, :]) * B + bm[ok]) * C + lab[ok][:, None]
-        msk = torch.ones_like(idx, dtype=torch.bool)
-        if feat_mask is not None:
-            words = feat_mask.long()[rs]
-            msk = ((words[:, fr // 32] >> (fr % 32)) & 1).bool()
-        wx = w[ok][:, None].expand_as(idx)
-        flat += torch.bincount(idx[msk], weights=wx[msk], minlength=flat.shape[0])
+    _hist_host(bins, d, node, weight, build_slot, feat_mask, B, (lab >= 0) & (lab < C), C, lab, (None,),
+               out.view(-1, 1))
     return out
 
 
@@ -849,40 +870,23 @@ def hist_codes(mode: int, bins: torch.Tensor, d: int, codes: torch.Tensor, tfirs
         if mode == 0:
             return hist_moments(bins, d, node, w, v0, v1, build_slot, slot_tree, feat_mask, B)
         return hist_classes(bins, d, node, w, label, C, build_slot, slot_tree, feat_mask, B)
-    lib = _lib.lib()
-    maxt = int(lib.cdna_hist5_max_trees())
+    maxt = int(_lib.lib().cdna_hist5_max_trees())
     packed = HIST5_PACKED and mode == 0 and v0 is None
     compact = packed and HIST5_COMPACT
     kbits = mode | (4 if (mode == 0 and v0 is not None) else 0) | (16 if packed else 0) | (64 if compact else 0)
-    per_slot = 8 * B * int(lib.cdna_hist4_bytes_per_bin(kbits, int(C)))
-    if per_slot > 150 * 1024:
-        raise ValueError("histogram too large for LDS (classes x bins)")
+    per_slot = _hist_per_slot(kbits, C, B)
     budget = lds_budget or HIST_LDS_BUDGET
     if packed:
         # register drain holds <= 16 cells per thread: 512 threads -> 64 KB, 1024 threads -> 128 KB
         budget = min(HIST5_PACKED_LDS if lds_budget is None else lds_budget, 16384 * 8)
         maxt = min(maxt, HIST5_PACKED_MAXT)
     SB = max(1, min(S, budget // per_slot))
-    slot_tree = np.asarray(slot_tree)
-    id_tree = np.asarray(id_tree)
-    rows = []
-    a = 0
-    while a < S:
-        b = min(S, a + SB)
-        # at most `maxt` trees per group (prefetched row record)
-        t0 = int(slot_tree[a])
-        b = min(b, int(np.searchsorted(slot_tree, t0 + maxt, side="left")))
-        t1 = int(slot_tree[b - 1])
-        i0 = int(np.searchsorted(id_tree, t0, side="left"))
-        i1 = int(np.searchsorted(id_tree, t1, side="right"))
-        rows.append((a, t0, t1, i0, i1))
-        a = b
-    grp, = upload(bins.device, np.asarray(rows, dtype=np.int32).reshape(-1))
+    # at most `maxt` trees per group (prefetched row record)
+    rows = slot_groups(slot_tree, id_tree, SB, maxt)
     ng = len(rows)
     # the tree cap can leave groups smaller than the LDS budget allows: size LDS to the largest group
     SB = max(min(SB, (rows[i + 1][0] if i + 1 < ng else S) - rows[i][0]) for i in range(ng))
     max_nt = max(r[2] - r[1] + 1 for r in rows)
-    bucket = 1 if max_nt <= 1 else 2 if max_nt <= 2 else 4 if max_nt <= 4 else 8 if max_nt <= 8 else 16
     big = packed and SB * per_slot > 8192 * 8  # 1024-thread blocks: 1 per CU
     # wave compaction pays once the plane needs 1024-thread blocks and several trees share
     # a pass (measured per level: profiles/hist_micro_1e8_compact.txt); below that the
@@ -890,34 +894,19 @@ def hist_codes(mode: int, bins: torch.Tensor, d: int, codes: torch.Tensor, tfirs
     compact = compact and (HIST5_COMPACT >= 2 or (big and max_nt >= 2))
     kbits = kbits if compact else (kbits & ~64)
     rbuf = 16 * 128 * 12 if compact else 0
-    lds_used = ((SB * per_slot + 15) // 16) * 16 + rbuf + bucket * 512 + SB + 16
+    lds_used = ((SB * per_slot + 15) // 16) * 16 + rbuf + _nt_bucket(max_nt) * 512 + SB + 16
     if lds_used > 160 * 1024:
         raise ValueError("local-node tables do not fit in LDS next to the histogram")
-    target_blocks = 512 if big else 1024
-    nchunk = int(max(1, min((target_blocks + G * ng - 1) // (G * ng), (n + 8191) // 8192)))
-    nchunk = max(nchunk, -(-n // (1 << 23)))
-    mw = 0 if feat_mask is None else feat_mask.shape[1]
-    fm = None if feat_mask is None else feat_mask.int().contiguous()
-    v0 = None if v0 is None else v0.float().contiguous()
-    v1 = None if v1 is None else v1.float().contiguous()
-    label = None if label is None else label.int().contiguous()
     wmax = int(max(1, min(255, wmax)))
-    qs0 = _fixed_scale(v0, n, wmax, qmax_bits=30)
-    qs1 = _packed_scale(v1) if packed else _fixed_scale(v1, n, wmax, qmax_bits=30)
-    iout = torch.zeros(out.shape, dtype=torch.int64, device=bins.device)
     assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.shape[1] == n
     tf = (upload(bins.device, tfirst.numpy().astype(np.int32))[0] if not tfirst.is_cuda else
           tfirst.to(dtype=torch.int32).contiguous())
-    bs = build_slot.int().contiguous()
-    _lib.check(lib.cdna_hist5(kbits, _ptr(bins), n, d, T, _ptr(codes), _ptr(tf), _ptr(v0), _ptr(v1), _ptr(label),
-                              int(C), _ptr(bs), _ptr(fm), mw, S, B, SB, _ptr(grp), ng, nchunk, max_nt, qs0, qs1,
-                              int(max(1, min(255, wmax))), _ptr(iout), _stream(bins.device)), "cdna_hist5")
-    out.copy_(iout)
-    if mode == 0:
-        if v0 is not None:
-            out[..., 0] /= qs0
-        out[..., 1] /= qs1
-    return out
+
+    def scales(v0, v1):
+        return (_fixed_scale(v0, n, wmax, qmax_bits=30),
+                _packed_scale(v1) if packed else _fixed_scale(v1, n, wmax, qmax_bits=30))
+    return _hist_launch("hist5", kbits, bins, d, T, (_ptr(codes), _ptr(tf)), v0, v1, label, C, build_slot,
+                        feat_mask, S, B, SB, rows, 512 if big else 1024, max_nt, scales, (wmax,), out)
 
 
 # persistent partition (tables staged once per block, coalesced bins words, all trees' codes in flight)
@@ -2001,7 +1990,7 @@ def seg_scales(v0p: Optional[torch.Tensor], v1p: torch.Tensor, wmax: int, n_glob
     With ``comm`` the max |v|, the max weight and ``n_global`` are agreed over every rank first: all ranks
     then quantise identically and their int64 histograms all-reduce to the same sums on 1 or N GPUs."""
     if v0p is None:
-        return 1.0, (packed_scale_global(v1p, comm) if comm is not None else _packed_scale(v1p))
+        return 1.0, packed_scale_global(v1p, comm)
     if comm is None or not comm.distributed:
         return (_fixed_scale(v0p, n_global, wmax, qmax_bits=30), _fixed_scale(v1p, n_global, wmax, qmax_bits=30))
     m = torch.tensor([_absmax(v0p) if v0p.numel() else 0.0,

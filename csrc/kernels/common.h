@@ -170,4 +170,15 @@ inline unsigned resident_blocks(const void* k, int threads, size_t lds) {
   return (unsigned)(per_cu * ncu);
 }
 
+// Dynamic LDS above the 64 KB default: raised to `bytes` (the kernel's widest plan) once per kernel instantiation
+// (`raised`: its static bool[64]) and device.
+inline int raise_lds(const void* fn, bool* raised, size_t bytes) {
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && raised[dev]) return 0;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) return (int)e;
+  if (dev >= 0 && dev < 64) raised[dev] = true;
+  return 0;
+}
+
 }  // namespace cdna

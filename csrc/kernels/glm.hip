@@ -351,8 +351,8 @@ int glm_launch(const GlmPlan& pl, const float* X, int64_t n, int d, int64_t ldx,
   // the dynamic LDS passes the 64 KB default at d + 2 > 96: raised to the widest plan's size, once per
   // instantiation and device
   static bool raised[64] = {};
-  const int rc = raise_lds(reinterpret_cast<const void*>(glm_step_kernel<PW, VW>), raised,
-                           glm_plan(1, kMaxD - 2).lds);
+  const int rc = cdna::raise_lds(reinterpret_cast<const void*>(glm_step_kernel<PW, VW>), raised,
+                                 glm_plan(1, kMaxD - 2).lds);
   if (rc != 0) return rc;
   hipLaunchKernelGGL((glm_step_kernel<PW, VW>), dim3(pl.nblk), dim3(256), pl.lds, st, X, n, d, ldx, y, w, off, beta,
                      b0, shift, zshift, sp, mode, pl.T, pl.npairs, pl.LD, ws, sws, pl.rows_per_block);

@@ -387,8 +387,8 @@ int resp_launch(const GmmPlan& pl, const float* X, int64_t n, int d, int64_t ldx
                 const float* AT, const double* corr, const double* logc, int k, int mode, float* sr, double* R,
                 int* assign, double* spart, hipStream_t st) {
   static bool raised[64] = {};
-  const int rc = raise_lds(reinterpret_cast<const void*>(gmm_resp_kernel<VW>), raised,
-                           gmm_plan(1, kMaxD - 1, kMaxK).lds_r);
+  const int rc = cdna::raise_lds(reinterpret_cast<const void*>(gmm_resp_kernel<VW>), raised,
+                                 gmm_plan(1, kMaxD - 1, kMaxK).lds_r);
   if (rc != 0) return rc;
   hipLaunchKernelGGL((gmm_resp_kernel<VW>), dim3(pl.nblk), dim3(256), pl.lds_r, st, X, n, d, ldx, w, cf, AT, corr,
                      logc, k, mode, pl.dk, pl.dc, pl.LDr, sr, R, assign, spart, pl.rows_per_block);

@@ -571,7 +571,7 @@ int launch_direct(const GramPlan& pl, const float* X, int64_t n, int d, const fl
   const int Dpad = ((pl.D + 31) / 32) * 32;
   const auto lds = [](int dpad) { return (size_t)kDStages * CPW * kDWaves * 1024 + (size_t)dpad * (kDRows + 8) * 2; };
   static bool raised[64] = {};  // the ring passes the 64 KB default: raised to the instantiation's widest plan
-  const int rc = raise_lds(reinterpret_cast<const void*>(gram_bf16d_kernel<PW, CPW>), raised, lds(128));
+  const int rc = cdna::raise_lds(reinterpret_cast<const void*>(gram_bf16d_kernel<PW, CPW>), raised, lds(128));
   if (rc != 0) return rc;
   hipLaunchKernelGGL((gram_bf16d_kernel<PW, CPW>), dim3(pl.nblk), dim3(256), lds(Dpad), st, X, n, d, y, shift, yshift,
                      pl.tab, pl.npairs, Dpad, ws, pl.rows_per_unit);

@@ -17,35 +17,21 @@
 // float atomics never had.  Quantisation step = 2^-s ~ max|v| * 2^-27 at
 // n = 1e8 (finer than a float32 ulp of max|v|).
 //
-// Lane mapping, block decode and LDS slot/mask staging follow hist2.hip (v2):
-// one block = (8-feature group g, slot group, row chunk); lanes own rows and
-// loop over the 8 features of their bins word.  (Measured and removed: the v3
+// One block = (8-feature group g, slot group, row chunk), decoded, staged and
+// flushed by histblock.h; lanes own rows and loop over the 8 features of
+// their bins word.  (Measured and removed: the v3
 // lane = 8 * row + feature mapping, a rotated-feature pipelined variant and a
 // packed single-atomic variant -- the fast kernel hist4f below replaced them.)
-#include "common.h"
+#include "histblock.h"
 
 namespace {
 
-struct Hist4Args {
-  const uint64_t* bins;
-  int64_t n;
-  int d, T;
-  const int* node;
-  const uint8_t* weight;
-  const float* v0;
-  const float* v1;
-  const int* label;
-  int C;
-  const int* build_slot;
-  const uint32_t* feat_mask;
-  int mask_words, S, B, SB, K;
-  const int* grp;  // [ngroups][5] = s0, t0, t1, id0, id1
-  int ngroups, nchunk;
-  int64_t rows_per_chunk;
-  int id_span_max;
-  float qs0, qs1;      // fixed-point scales (powers of two) for v0, v1
-  int n64, n32;        // planes held as 64-bit / 32-bit integers in LDS
-  unsigned long long* out;  // [S][d][B][K] int64
+using namespace cdna;
+
+struct Hist4Args : HistArgs {
+  const int* node;        // [T][n] active node id or -1
+  const uint8_t* weight;  // [T][n] or null (weight 1)
+  int id_span_max;        // entries of the LDS slot table
 };
 
 constexpr int kThreads = 512;
@@ -60,42 +46,24 @@ __device__ __forceinline__ void lds_add64(unsigned long long* p, long long v) {
 template <int MODE, bool V0>
 __global__ __launch_bounds__(kThreads) void hist4_kernel(const Hist4Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int G = (a.d + 7) / 8;
   const int plane = a.SB * 8 * a.B;
-  unsigned long long* h64 = reinterpret_cast<unsigned long long*>(smem);
-  uint32_t* h32 = reinterpret_cast<uint32_t*>(h64 + (size_t)a.n64 * plane);
-  const int hwords = a.n32 * plane;  // 32-bit words of h32
-  int* lslot = reinterpret_cast<int*>(h32 + ((hwords + 3) & ~3));
+  const HistBlock blk = hist_block(a);
+  const HistLds lds = hist_lds(smem, a.n64, a.n32, plane);
+  unsigned long long* h64 = lds.h64;
+  uint32_t* h32 = lds.h32;
+  int* lslot = reinterpret_cast<int*>(lds.rest);
   uint8_t* lmask = reinterpret_cast<uint8_t*>(lslot + a.id_span_max);
-
-  const uint32_t w = cdna::xcd_remap(blockIdx.x, gridDim.x);
-  const int g = (int)(w % G);
-  const int grp = (int)((w / G) % a.ngroups);
-  const int chunk = (int)(w / ((uint32_t)G * a.ngroups));
-  const int s0 = a.grp[grp * 5 + 0], t0 = a.grp[grp * 5 + 1], t1 = a.grp[grp * 5 + 2];
-  const int id0 = a.grp[grp * 5 + 3], id1 = a.grp[grp * 5 + 4];
+  const int g = blk.g, s0 = blk.s0, t0 = blk.t0, t1 = blk.t1, id0 = blk.id0, id1 = blk.id1;
   const int span = id1 - id0;
   const bool lds_slot = span <= a.id_span_max;
-  const int fbase = g * 8;
 
-  for (int i = threadIdx.x; i < a.n64 * plane; i += kThreads) h64[i] = 0ull;
-  for (int i = threadIdx.x; i < hwords; i += kThreads) h32[i] = 0u;
+  hist_clear<kThreads>(lds, a.n64, a.n32, plane);
   if (lds_slot)
     for (int i = threadIdx.x; i < span; i += kThreads) lslot[i] = a.build_slot[id0 + i];
-  for (int i = threadIdx.x; i < a.SB; i += kThreads) {
-    uint32_t m = 0xFFu;
-    const int slot = s0 + i;
-    if (a.feat_mask != nullptr && slot < a.S)
-      m = (a.feat_mask[(int64_t)slot * a.mask_words + (fbase >> 5)] >> (fbase & 31)) & 0xFFu;
-    const int valid = a.d - fbase;
-    if (valid < 8) m &= (1u << (valid > 0 ? valid : 0)) - 1u;
-    lmask[i] = (uint8_t)m;
-  }
+  hist_stage_mask<kThreads, true>(lmask, a, blk);
   __syncthreads();
 
-  const int64_t rb = (int64_t)chunk * a.rows_per_chunk;
-  int64_t re = rb + a.rows_per_chunk;
-  if (re > a.n) re = a.n;
+  const int64_t rb = blk.rb, re = blk.re;
   const int64_t n = a.n;
   for (int64_t r = rb + threadIdx.x; r < re; r += kThreads) {
     const uint64_t b8 = a.bins[(int64_t)g * n + r];
@@ -150,30 +118,7 @@ __global__ __launch_bounds__(kThreads) void hist4_kernel(const Hist4Args a) {
     }
   }
   __syncthreads();
-  // flush: entry e of plane p -> out[slot][f][bin][k]
-  const int total = (a.n64 + a.n32) * plane;
-  for (int i = threadIdx.x; i < total; i += kThreads) {
-    const bool is64 = i < a.n64 * plane;
-    const int p = is64 ? i / plane : (i - a.n64 * plane) / plane;
-    const int rem = i - (is64 ? p : a.n64 + p) * plane;
-    long long v;
-    int k;
-    if (is64) {
-      v = (long long)h64[i];
-      k = (MODE == 0 && !V0) ? 1 : p;
-    } else {
-      v = (long long)h32[i - a.n64 * plane];
-      k = p;
-    }
-    if (v == 0) continue;
-    const int ls = rem / (8 * a.B);
-    const int jj = (rem / a.B) & 7;
-    const int bn = rem % a.B;
-    const int f = fbase + jj;
-    const int slot = s0 + ls;
-    if (f < a.d && slot < a.S)
-      atomicAdd(&a.out[(((int64_t)slot * a.d + f) * a.B + bn) * a.K + k], (unsigned long long)v);
-  }
+  hist_flush_planes<MODE == 0 && !V0, kThreads>(a, blk, lds, plane);
 }
 
 // ---------------------------------------------------------------------------
@@ -192,50 +137,24 @@ __global__ __launch_bounds__(kThreads) void hist4_kernel(const Hist4Args a) {
 template <int MODE, bool MASKED>
 __global__ __launch_bounds__(kThreads) void hist4f_kernel(const Hist4Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int G = (a.d + 7) / 8;
   const int plane = a.SB * 8 * a.B;
-  unsigned long long* h64 = reinterpret_cast<unsigned long long*>(smem);
-  uint32_t* h32 = reinterpret_cast<uint32_t*>(h64 + (size_t)a.n64 * plane);
-  const int hwords = a.n32 * plane;
-  int* lslot = reinterpret_cast<int*>(h32 + ((hwords + 3) & ~3));
+  const HistBlock blk = hist_block(a);
+  const HistLds lds = hist_lds(smem, a.n64, a.n32, plane);
+  unsigned long long* h64 = lds.h64;
+  uint32_t* h32 = lds.h32;
+  int* lslot = reinterpret_cast<int*>(lds.rest);
   uint8_t* lmask = reinterpret_cast<uint8_t*>(lslot + a.id_span_max);
-
-  const uint32_t w = cdna::xcd_remap(blockIdx.x, gridDim.x);
-  const int g = (int)(w % G);
-  const int grp = (int)((w / G) % a.ngroups);
-  const int chunk = (int)(w / ((uint32_t)G * a.ngroups));
-  const int s0 = a.grp[grp * 5 + 0], t0 = a.grp[grp * 5 + 1], t1 = a.grp[grp * 5 + 2];
-  const int id0 = a.grp[grp * 5 + 3], id1 = a.grp[grp * 5 + 4];
-  const int span = id1 - id0;
-  const int fbase = g * 8;
+  const int g = blk.g, s0 = blk.s0, t0 = blk.t0, t1 = blk.t1, id0 = blk.id0, id1 = blk.id1;
+  const int span = id1 - id0;  // <= id_span_max (the host picks this kernel only then)
   const int rot = threadIdx.x & 7;
 
-  for (int i = threadIdx.x; i < a.n64 * plane; i += kThreads) h64[i] = 0ull;
-  for (int i = threadIdx.x; i < hwords; i += kThreads) h32[i] = 0u;
+  hist_clear<kThreads>(lds, a.n64, a.n32, plane);
   for (int i = threadIdx.x; i < span; i += kThreads) lslot[i] = a.build_slot[id0 + i];
-  for (int i = threadIdx.x; i < a.SB; i += kThreads) {
-    uint32_t m = 0xFFu;
-    const int slot = s0 + i;
-    if (a.feat_mask != nullptr && slot < a.S)
-      m = (a.feat_mask[(int64_t)slot * a.mask_words + (fbase >> 5)] >> (fbase & 31)) & 0xFFu;
-    const int valid = a.d - fbase;
-    if (valid < 8) m &= (1u << (valid > 0 ? valid : 0)) - 1u;
-    lmask[i] = (uint8_t)m;
-  }
-  // per-thread constants of the rotated feature order
-  int fsel[8], fsh[8], foff[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int jj = (j + rot) & 7;
-    fsel[j] = jj >> 2;              // which 32-bit half of the bins word
-    fsh[j] = (jj & 3) * 8;          // byte position inside it
-    foff[j] = jj * a.B;             // feature row inside the slot's [8][B] block
-  }
+  hist_stage_mask<kThreads, true>(lmask, a, blk);
+  const HistRot fr = hist_rot(rot, a.B);
   __syncthreads();
 
-  const int64_t rb = (int64_t)chunk * a.rows_per_chunk;
-  int64_t re = rb + a.rows_per_chunk;
-  if (re > a.n) re = a.n;
+  const int64_t rb = blk.rb, re = blk.re;
   const int64_t n = a.n;
   const int nt_head = t1 - t0 + 1 < 4 ? t1 - t0 + 1 : 4;
   const int slot_cells = 8 * a.B;
@@ -273,7 +192,7 @@ __global__ __launch_bounds__(kThreads) void hist4f_kernel(const Hist4Args a) {
     int cell[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      cell[j] = foff[j] + (int)__builtin_amdgcn_ubfe(fsel[j] ? hi : lo, (uint32_t)fsh[j], 8u);
+      cell[j] = fr.foff[j] + (int)__builtin_amdgcn_ubfe(fr.fsel[j] ? hi : lo, (uint32_t)fr.fsh[j], 8u);
     int q = 0;
     bool row_ok = true;
     if (MODE == 0) q = (int)rintf(x1 * a.qs1);
@@ -311,7 +230,7 @@ __global__ __launch_bounds__(kThreads) void hist4f_kernel(const Hist4Args a) {
           if (ls < 0 || ls >= a.SB) continue;
           const uint32_t base = (uint32_t)(ls * slot_cells) + cbase_lab;
           uint32_t mrot = 0xFFu;
-          if (MASKED) mrot = ((mk[k] >> rot) | (mk[k] << (8 - rot))) & 0xFFu;
+          if (MASKED) mrot = rot8(mk[k], rot);
           const uint32_t wv = (uint32_t)cwt[k];
           const long long y1 = (long long)cwt[k] * (long long)q;
 #pragma unroll
@@ -331,34 +250,8 @@ __global__ __launch_bounds__(kThreads) void hist4f_kernel(const Hist4Args a) {
     for (int k = 0; k < 4; ++k) { ids[k] = nids[k]; wt[k] = nwt[k]; }
   }
   __syncthreads();
-  const int total = (a.n64 + a.n32) * plane;
-  for (int i = threadIdx.x; i < total; i += kThreads) {
-    const bool is64 = i < a.n64 * plane;
-    const int p = is64 ? i / plane : (i - a.n64 * plane) / plane;
-    const int rem = i - (is64 ? p : a.n64 + p) * plane;
-    long long v;
-    int k;
-    if (is64) {
-      v = (long long)h64[i];
-      k = 1;
-    } else {
-      v = (long long)h32[i - a.n64 * plane];
-      k = p;
-    }
-    if (v == 0) continue;
-    const int ls = rem / (8 * a.B);
-    const int jj = (rem / a.B) & 7;
-    const int bn = rem % a.B;
-    const int f = fbase + jj;
-    const int slot = s0 + ls;
-    if (f < a.d && slot < a.S)
-      atomicAdd(&a.out[(((int64_t)slot * a.d + f) * a.B + bn) * a.K + k], (unsigned long long)v);
-  }
-}
-
-template <int MODE, bool V0>
-void launch(const Hist4Args& a, unsigned nblk, size_t lds, hipStream_t st) {
-  hipLaunchKernelGGL((hist4_kernel<MODE, V0>), dim3(nblk), dim3(kThreads), lds, st, a);
+  // the one 64-bit plane (moments) is the sum: out plane 1
+  hist_flush_planes<true, kThreads>(a, blk, lds, plane);
 }
 
 }  // namespace
@@ -381,54 +274,23 @@ CDNA_API int cdna_hist4(int mode, const uint64_t* bins, int64_t n, int d, int T,
                         unsigned long long* out, hipStream_t st) {
   if (n <= 0 || S <= 0) return 0;
   Hist4Args a;
-  a.bins = bins;
-  a.n = n;
-  a.d = d;
-  a.T = T;
+  const int rc = hist_fill(a, mode, bins, n, d, T, v0, v1, label, C, build_slot, feat_mask, mask_words, S, B, SB, grp,
+                           ngroups, nchunk, qs0, qs1, out);
+  if (rc != 0) return rc;
   a.node = node;
   a.weight = weight;
-  a.v0 = v0;
-  a.v1 = v1;
-  a.label = label;
-  a.C = C;
-  a.build_slot = build_slot;
-  a.feat_mask = feat_mask;
-  a.mask_words = mask_words;
-  a.S = S;
-  a.B = B;
-  a.SB = SB;
-  const bool classes = (mode & 1) != 0, has_v0 = (mode & 4) != 0;
-  a.K = classes ? C : 2;
-  a.n64 = classes ? 0 : (has_v0 ? 2 : 1);
-  a.n32 = classes ? C : (has_v0 ? 0 : 1);
-  a.grp = grp;
-  a.ngroups = ngroups;
-  a.nchunk = nchunk;
-  a.rows_per_chunk = (n + nchunk - 1) / nchunk;
-  // u32 LDS counts: at most rows_per_chunk * 255 per word
-  if (a.rows_per_chunk * 255 >= (int64_t)1 << 32) return (int)hipErrorInvalidValue;
   a.id_span_max = id_span_max;
-  a.qs0 = qs0;
-  a.qs1 = qs1;
-  a.out = out;
-  const int G = (d + 7) / 8;
-  const size_t plane = (size_t)SB * 8 * B;
-  const size_t lds = plane * 8 * a.n64 + ((plane * a.n32 + 3) & ~(size_t)3) * 4 + (size_t)id_span_max * 4 + SB + 16;
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  const unsigned nblk = (unsigned)G * ngroups * nchunk;
+  const bool classes = (mode & 1) != 0, has_v0 = (mode & 4) != 0, masked = feat_mask != nullptr;
+  const size_t lds = hist_plane_bytes(a) + (size_t)id_span_max * 4 + SB + 16;
+  const unsigned nblk = hist_blocks(a);
   if ((mode & 32) && !has_v0) {  // fast rotated kernel (moments without v0, or classes)
-    const bool masked = feat_mask != nullptr;
-    if (classes) {
-      if (masked) hipLaunchKernelGGL((hist4f_kernel<1, true>), dim3(nblk), dim3(kThreads), lds, st, a);
-      else hipLaunchKernelGGL((hist4f_kernel<1, false>), dim3(nblk), dim3(kThreads), lds, st, a);
-    } else {
-      if (masked) hipLaunchKernelGGL((hist4f_kernel<0, true>), dim3(nblk), dim3(kThreads), lds, st, a);
-      else hipLaunchKernelGGL((hist4f_kernel<0, false>), dim3(nblk), dim3(kThreads), lds, st, a);
-    }
-    return (int)hipGetLastError();
+    if (classes)
+      return masked ? hist_launch<hist4f_kernel<1, true>>(nblk, kThreads, lds, st, a)
+                    : hist_launch<hist4f_kernel<1, false>>(nblk, kThreads, lds, st, a);
+    return masked ? hist_launch<hist4f_kernel<0, true>>(nblk, kThreads, lds, st, a)
+                  : hist_launch<hist4f_kernel<0, false>>(nblk, kThreads, lds, st, a);
   }
-  if (classes) launch<1, false>(a, nblk, lds, st);
-  else if (has_v0) launch<0, true>(a, nblk, lds, st);
-  else launch<0, false>(a, nblk, lds, st);
-  return (int)hipGetLastError();
+  if (classes) return hist_launch<hist4_kernel<1, false>>(nblk, kThreads, lds, st, a);
+  if (has_v0) return hist_launch<hist4_kernel<0, true>>(nblk, kThreads, lds, st, a);
+  return hist_launch<hist4_kernel<0, false>>(nblk, kThreads, lds, st, a);
 }

@@ -16,38 +16,29 @@
 // tree t, a per-level table).  Rows with zero
 // bootstrap weight are "done" from the start and never touch LDS.  The
 // histogram inner loop is hist4f's (rotated features, hoisted VALU work,
-// batched slot-table reads); the next row's record is prefetched.
-#include "common.h"
+// batched slot-table reads); the next row's record is prefetched.  The block
+// scaffolding around the row loops of the packed kernels is histblock.h's.
+#include "histblock.h"
 #include "packed.h"
 
 namespace {
 
+using namespace cdna;
+
 constexpr int kThreads = 512;
 constexpr int kMaxTrees = 16;  // trees per block group (host splits larger groups)
 
-struct Hist5Args {
-  const uint64_t* bins;  // [G][n] 8 bins per word
-  int64_t n;
-  int d, T;
+struct Hist5Args : HistArgs {
   const uint16_t* codes;  // [T][n]
   const int* tfirst;      // [T] first active id of each tree at this level
-  const float* v0;
-  const float* v1;
-  const int* label;
-  int C;
-  const int* build_slot;  // [A] slot or -1
-  const uint32_t* feat_mask;
-  int mask_words, S, B, SB, K;
-  const int* grp;  // [ngroups][5] = s0, t0, t1, id0, id1
-  int ngroups, nchunk;
-  int64_t rows_per_chunk;
-  float qs0, qs1;
-  int n64, n32;
-  int drain_iters;          // packed kernel: row iterations between register drains
-  unsigned long long* out;  // [S][d][B][K]
+  int drain_iters;        // packed kernels: row iterations between register drains
 };
 
 // MODE 0: moments (count u32 + sum u64, or with V0 two u64 sums); MODE 1: class counts (u32).
+// This kernel keeps its own block scaffolding (decode, LDS carve-up, clears, tables, flush), as it was before
+// histblock.h: written through the shared helpers, with a row loop that compiles to the same instructions, its
+// 16-trees-per-group level-0 pass measured 0.03-0.1 ms (up to 0.8 %) slower than before in most timing jobs, and the
+// piece responsible could not be isolated (profiles/r13/histblock.md).  The packed kernels below share all of it.
 template <int MODE, bool MASKED, bool V0, int NT>
 __global__ __launch_bounds__(kThreads) void hist5_kernel(const Hist5Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -269,28 +260,18 @@ template <bool MASKED, int NT, int TH>
 __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
   // rows between drains: (rows x max weight) < 2^20 keeps both packed fields in range
   const int drain_iters = a.drain_iters;
-  constexpr int MODE = 0;
-  constexpr bool V0 = false;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int G = (a.d + 7) / 8;
   const int plane = a.SB * 8 * a.B;
-  unsigned long long* h64 = reinterpret_cast<unsigned long long*>(smem);
-  uint32_t* h32 = reinterpret_cast<uint32_t*>(h64 + (size_t)plane);
-  const int hwords = 0;
-  // per-tree local-node -> slot table: lt[k][loc] = slot - s0 or -1 (loc 255 = done)
-  int16_t* lt = reinterpret_cast<int16_t*>(h32 + ((hwords + 3) & ~3));
-  const uint32_t w = cdna::xcd_remap(blockIdx.x, gridDim.x);
-  const int g = (int)(w % G);
-  const int grp = (int)((w / G) % a.ngroups);
-  const int chunk = (int)(w / ((uint32_t)G * a.ngroups));
-  const int s0 = a.grp[grp * 5 + 0], t0 = a.grp[grp * 5 + 1], t1 = a.grp[grp * 5 + 2];
-  const int id1 = a.grp[grp * 5 + 4];
-  const int nt = t1 - t0 + 1;  // <= kMaxTrees (host-checked)
+  const HistBlock blk = hist_block(a);
+  const HistLds lds = hist_lds(smem, 1, 0, plane);  // one plane of packed cells
+  unsigned long long* h64 = lds.h64;
+  int16_t* lt = reinterpret_cast<int16_t*>(lds.rest);
   uint8_t* lmask = reinterpret_cast<uint8_t*>(lt + NT * 256);
-  const int fbase = g * 8;
+  const int g = blk.g, t0 = blk.t0;
+  const int nt = blk.t1 - t0 + 1;  // <= kMaxTrees (host-checked)
   const int rot = threadIdx.x & 7;
 
-  for (int i = threadIdx.x; i < plane; i += TH) h64[i] = 0ull;
+  hist_clear<TH>(lds, 1, 0, plane);
   uint32_t acc_c[kPackCells];
   long long acc_s[kPackCells];
 #pragma unroll
@@ -298,70 +279,32 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
     acc_c[i] = 0u;
     acc_s[i] = 0;
   }
-  for (int i = threadIdx.x; i < hwords; i += TH) h32[i] = 0u;
-  for (int i = threadIdx.x; i < NT * 256; i += TH) {
-    const int k = i >> 8, loc = i & 255;
-    int v = -1;
-    const int id = k < nt ? a.tfirst[t0 + k] + loc : 0;
-    const int idend = k + 1 < nt ? a.tfirst[t0 + k + 1] : id1;
-    if (k < nt && loc != 255 && id < idend) {
-      const int sl = a.build_slot[id];
-      if (sl >= s0 && sl < s0 + a.SB) v = sl - s0;
-    }
-    lt[i] = (int16_t)v;
-  }
-  if (MASKED) {
-    for (int i = threadIdx.x; i < a.SB; i += TH) {
-      const int slot = s0 + i;
-      uint32_t m = 0u;
-      if (slot < a.S) m = (a.feat_mask[(int64_t)slot * a.mask_words + (fbase >> 5)] >> (fbase & 31)) & 0xFFu;
-      const int valid = a.d - fbase;
-      if (valid < 8) m &= (1u << (valid > 0 ? valid : 0)) - 1u;
-      lmask[i] = (uint8_t)m;
-    }
-  }
-  int fsel[8], fsh[8], foff[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int jj = (j + rot) & 7;
-    fsel[j] = jj >> 2;
-    fsh[j] = (jj & 3) * 8;
-    foff[j] = jj * a.B;
-  }
-  // features beyond d in the last block
-  const int valid_f = a.d - fbase;
-  uint32_t fvalid = valid_f >= 8 ? 0xFFu : ((1u << (valid_f > 0 ? valid_f : 0)) - 1u);
-  const uint32_t frot = ((fvalid >> rot) | (fvalid << (8 - rot))) & 0xFFu;
-  const bool all8 = valid_f >= 8;
+  hist_local_tables<NT, TH>(lt, a, a.tfirst, blk);
+  if (MASKED) hist_stage_mask<TH, false>(lmask, a, blk);
+  const HistRot fr = hist_rot(rot, a.B);
+  const uint32_t frot = hist_frot(a, blk.fbase, rot);
+  const bool all8 = hist_all8(a, blk.fbase);
   __syncthreads();
 
-  const int64_t rb = (int64_t)chunk * a.rows_per_chunk;
-  int64_t re = rb + a.rows_per_chunk;
-  if (re > a.n) re = a.n;
+  const int64_t rb = blk.rb, re = blk.re;
   const int64_t n = a.n;
   const int slot_cells = 8 * a.B;
 
   uint64_t b8 = 0;
-  float x0 = 1.f, x1 = 0.f;
-  int lab = 0;
+  float x1 = 0.f;
   uint32_t cd[NT];
   // trees past nt read a valid row (their tables are all -1, so they never add)
   const int64_t tstride = (int64_t)n;
-  auto load_row = [&](int64_t rr, uint64_t& ob8, float& ox0, float& ox1, int& olab, uint32_t* ocd) {
+  auto load_row = [&](int64_t rr, uint64_t& ob8, float& ox1, uint32_t* ocd) {
     ob8 = a.bins[(int64_t)g * n + rr];
-    if (MODE == 0) {
-      if (V0) ox0 = a.v0[rr];
-      ox1 = a.v1[rr];
-    } else {
-      olab = a.label[rr];
-    }
+    ox1 = a.v1[rr];
     const uint16_t* cp = a.codes + (int64_t)t0 * n + rr;
 #pragma unroll
     for (int k = 0; k < NT; ++k) ocd[k] = (uint32_t)cp[(k < nt ? k : 0) * tstride];
   };
   auto drain = [&]() { drain_packed<TH>(h64, plane, acc_c, acc_s); };
   int64_t r = rb + threadIdx.x;
-  if (r < re) load_row(r, b8, x0, x1, lab, cd);
+  if (r < re) load_row(r, b8, x1, cd);
   else {
 #pragma unroll
     for (int k = 0; k < NT; ++k) cd[k] = 0xFFu;
@@ -374,11 +317,10 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
       for (int k = 0; k < NT; ++k) cd[k] = 0xFFu;  // tail lanes: no work, but keep the block in step
     }
     uint64_t nb8 = 0;
-    float nx0 = 1.f, nx1 = 0.f;
-    int nlab = 0;
+    float nx1 = 0.f;
     uint32_t ncd[NT];
     const int64_t rn = r + TH;
-    if (rn < re) load_row(rn, nb8, nx0, nx1, nlab, ncd);
+    if (rn < re) load_row(rn, nb8, nx1, ncd);
     else {
 #pragma unroll
       for (int k = 0; k < NT; ++k) ncd[k] = 0xFFu;
@@ -388,11 +330,9 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
     int cell[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      cell[j] = foff[j] + (int)__builtin_amdgcn_ubfe(fsel[j] ? hi : lo, (uint32_t)fsh[j], 8u);
+      cell[j] = fr.foff[j] + (int)__builtin_amdgcn_ubfe(fr.fsel[j] ? hi : lo, (uint32_t)fr.fsh[j], 8u);
     const unsigned long long qoff = cdna::pack_quant(x1, a.qs1);
-    const bool row_ok = true;
-    const uint32_t cbase_lab = MODE == 1 ? (uint32_t)(lab * plane) : 0u;
-    if (row_ok) {
+    {
       constexpr int KB = NT;  // all slot-table reads of the row first: one LDS wait per row
 #pragma unroll
       for (int kb = 0; kb < NT; kb += KB) {
@@ -408,9 +348,9 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
           const int ls = lsk[k];
           if (ls < 0) continue;
           const uint32_t wv = cd[kb + k] >> 8;
-          const uint32_t base = (uint32_t)(ls * slot_cells) + cbase_lab;
+          const uint32_t base = (uint32_t)(ls * slot_cells);
           uint32_t mrot = frot;
-          if (MASKED) mrot &= ((mk[k] >> rot) | (mk[k] << (8 - rot))) & 0xFFu;
+          if (MASKED) mrot &= rot8(mk[k], rot);
           const unsigned long long add = cdna::cell_addend(wv, qoff);
           if (!MASKED && all8) {
 #pragma unroll
@@ -426,32 +366,14 @@ __global__ __launch_bounds__(TH) void hist5p_kernel(const Hist5Args a) {
       }
     }
     b8 = nb8;
-    x0 = nx0;
     x1 = nx1;
-    lab = nlab;
 #pragma unroll
     for (int k = 0; k < NT; ++k) cd[k] = ncd[k];
     if ((iter + 1) % drain_iters == 0) drain();
   }
   drain();
-#pragma unroll
-  for (int i = 0; i < kPackCells; ++i) {
-    const int idx = (int)threadIdx.x + i * TH;
-    if (idx >= plane || acc_c[i] == 0u) continue;
-    const int ls = idx / (8 * a.B);
-    const int jj = (idx / a.B) & 7;
-    const int bn = idx % a.B;
-    const int f = fbase + jj;
-    const int slot = s0 + ls;
-    if (f < a.d && slot < a.S) {
-      unsigned long long* o = &a.out[(((int64_t)slot * a.d + f) * a.B + bn) * 2];
-      atomicAdd(o, (unsigned long long)acc_c[i]);
-      atomicAdd(o + 1, (unsigned long long)acc_s[i]);
-    }
-  }
+  hist_flush_cells<TH>(a, blk, plane, acc_c, acc_s);
 }
-
-
 
 // Wave-compacted packed kernel.  An LDS atomic costs the same whatever
 // fraction of the wave is active (profiles/lds_mask_bench_mi355x.txt: 16 clk
@@ -474,25 +396,20 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
   const int drain_iters = a.drain_iters;
   constexpr int NW = TH / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int G = (a.d + 7) / 8;
   const int plane = a.SB * 8 * a.B;
-  unsigned long long* h64 = reinterpret_cast<unsigned long long*>(smem);
-  uint2* rbuf_b = reinterpret_cast<uint2*>(h64 + (size_t)plane);  // [NW][2][64] bins words
+  const HistBlock blk = hist_block(a);
+  const HistLds lds = hist_lds(smem, 1, 0, plane);  // one plane of packed cells
+  unsigned long long* h64 = lds.h64;
+  uint2* rbuf_b = reinterpret_cast<uint2*>(lds.rest);                 // [NW][2][64] bins words
   uint32_t* rbuf_q = reinterpret_cast<uint32_t*>(rbuf_b + NW * 128);  // [NW][2][64] q + 2^23
   int16_t* lt = reinterpret_cast<int16_t*>(rbuf_q + NW * 128);
   uint8_t* lmask = reinterpret_cast<uint8_t*>(lt + NT * 256);
-  const uint32_t w = cdna::xcd_remap(blockIdx.x, gridDim.x);
-  const int g = (int)(w % G);
-  const int grp = (int)((w / G) % a.ngroups);
-  const int chunk = (int)(w / ((uint32_t)G * a.ngroups));
-  const int s0 = a.grp[grp * 5 + 0], t0 = a.grp[grp * 5 + 1], t1 = a.grp[grp * 5 + 2];
-  const int id1 = a.grp[grp * 5 + 4];
-  const int nt = t1 - t0 + 1;
-  const int fbase = g * 8;
+  const int g = blk.g, t0 = blk.t0;
+  const int nt = blk.t1 - t0 + 1;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int rot = lane & 7;
 
-  for (int i = threadIdx.x; i < plane; i += TH) h64[i] = 0ull;
+  hist_clear<TH>(lds, 1, 0, plane);
   uint32_t acc_c[kPackCells];
   long long acc_s[kPackCells];
 #pragma unroll
@@ -500,44 +417,14 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
     acc_c[i] = 0u;
     acc_s[i] = 0;
   }
-  for (int i = threadIdx.x; i < NT * 256; i += TH) {
-    const int k = i >> 8, loc = i & 255;
-    int v = -1;
-    const int id = k < nt ? a.tfirst[t0 + k] + loc : 0;
-    const int idend = k + 1 < nt ? a.tfirst[t0 + k + 1] : id1;
-    if (k < nt && loc != 255 && id < idend) {
-      const int sl = a.build_slot[id];
-      if (sl >= s0 && sl < s0 + a.SB) v = sl - s0;
-    }
-    lt[i] = (int16_t)v;
-  }
-  if (MASKED) {
-    for (int i = threadIdx.x; i < a.SB; i += TH) {
-      const int slot = s0 + i;
-      uint32_t m = 0u;
-      if (slot < a.S) m = (a.feat_mask[(int64_t)slot * a.mask_words + (fbase >> 5)] >> (fbase & 31)) & 0xFFu;
-      const int valid = a.d - fbase;
-      if (valid < 8) m &= (1u << (valid > 0 ? valid : 0)) - 1u;
-      lmask[i] = (uint8_t)m;
-    }
-  }
-  int fsel[8], fsh[8], foff[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int jj = (j + rot) & 7;
-    fsel[j] = jj >> 2;
-    fsh[j] = (jj & 3) * 8;
-    foff[j] = jj * a.B;
-  }
-  const int valid_f = a.d - fbase;
-  const uint32_t fvalid = valid_f >= 8 ? 0xFFu : ((1u << (valid_f > 0 ? valid_f : 0)) - 1u);
-  const uint32_t frot = ((fvalid >> rot) | (fvalid << (8 - rot))) & 0xFFu;
-  const bool all8 = valid_f >= 8;  // block-uniform: no per-feature guards in the atomic rounds
+  hist_local_tables<NT, TH>(lt, a, a.tfirst, blk);
+  if (MASKED) hist_stage_mask<TH, false>(lmask, a, blk);
+  const HistRot fr = hist_rot(rot, a.B);
+  const uint32_t frot = hist_frot(a, blk.fbase, rot);
+  const bool all8 = hist_all8(a, blk.fbase);  // block-uniform: no per-feature guards in the atomic rounds
   __syncthreads();
 
-  const int64_t rb = (int64_t)chunk * a.rows_per_chunk;
-  int64_t re = rb + a.rows_per_chunk;
-  if (re > a.n) re = a.n;
+  const int64_t rb = blk.rb, re = blk.re;
   const int64_t n = a.n;
   const int slot_cells = 8 * a.B;
   uint2* my_b = rbuf_b + wid * 128;
@@ -555,19 +442,19 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
     uint32_t mr_ = frot;                                                                        \
     if (MASKED) {                                                                               \
       const uint32_t mk_ = lmask[ls_];                                                          \
-      mr_ &= ((mk_ >> rot) | (mk_ << (8 - rot))) & 0xFFu;                                       \
+      mr_ &= rot8(mk_, rot);                                                                    \
     }                                                                                           \
     const unsigned long long add_ = cdna::cell_addend(wv_, qo_);                                \
     unsigned long long* hb_ = h64 + ls_ * slot_cells;                                           \
     if (!MASKED && all8) {                                                                      \
       _Pragma("unroll") for (int j = 0; j < 8; ++j)                                             \
-        atomicAdd(hb_ + foff[j] + (int)__builtin_amdgcn_ubfe(fsel[j] ? bw_.y : bw_.x,           \
-                                                               (uint32_t)fsh[j], 8u), add_);    \
+        atomicAdd(hb_ + fr.foff[j] + (int)__builtin_amdgcn_ubfe(fr.fsel[j] ? bw_.y : bw_.x,     \
+                                                                  (uint32_t)fr.fsh[j], 8u), add_); \
     } else {                                                                                    \
       _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                           \
         if ((mr_ >> j) & 1u)                                                                    \
-          atomicAdd(hb_ + foff[j] + (int)__builtin_amdgcn_ubfe(fsel[j] ? bw_.y : bw_.x,         \
-                                                                 (uint32_t)fsh[j], 8u), add_);  \
+          atomicAdd(hb_ + fr.foff[j] + (int)__builtin_amdgcn_ubfe(fr.fsel[j] ? bw_.y : bw_.x,   \
+                                                                    (uint32_t)fr.fsh[j], 8u), add_); \
       }                                                                                         \
     }                                                                                           \
   }
@@ -662,21 +549,7 @@ __global__ __launch_bounds__(TH) void hist5q_kernel(const Hist5Args a) {
   H5Q_ROUND(qa, lane < cnt);
   drain();
 #undef H5Q_ROUND
-#pragma unroll
-  for (int i = 0; i < kPackCells; ++i) {
-    const int idx = (int)threadIdx.x + i * TH;
-    if (idx >= plane || acc_c[i] == 0u) continue;
-    const int ls = idx / (8 * a.B);
-    const int jj = (idx / a.B) & 7;
-    const int bn = idx % a.B;
-    const int f = fbase + jj;
-    const int slot = s0 + ls;
-    if (f < a.d && slot < a.S) {
-      unsigned long long* o = &a.out[(((int64_t)slot * a.d + f) * a.B + bn) * 2];
-      atomicAdd(o, (unsigned long long)acc_c[i]);
-      atomicAdd(o + 1, (unsigned long long)acc_s[i]);
-    }
-  }
+  hist_flush_cells<TH>(a, blk, plane, acc_c, acc_s);
 }
 
 // Row-record partition: every row moves, in every tree, from its active node to
@@ -945,61 +818,37 @@ inline unsigned grid_for(int64_t n, int per, unsigned cap) {
   return (unsigned)(b < (int64_t)cap ? (b < 1 ? 1 : b) : cap);
 }
 
-template <int MODE, bool MASKED, bool V0>
-void launch5(const Hist5Args& a, int nt_max, unsigned nblk, size_t lds, hipStream_t st) {
-  if (nt_max <= 1) hipLaunchKernelGGL((hist5_kernel<MODE, MASKED, V0, 1>), dim3(nblk), dim3(kThreads), lds, st, a);
-  else if (nt_max <= 2)
-    hipLaunchKernelGGL((hist5_kernel<MODE, MASKED, V0, 2>), dim3(nblk), dim3(kThreads), lds, st, a);
-  else if (nt_max <= 4)
-    hipLaunchKernelGGL((hist5_kernel<MODE, MASKED, V0, 4>), dim3(nblk), dim3(kThreads), lds, st, a);
-  else if (nt_max <= 8)
-    hipLaunchKernelGGL((hist5_kernel<MODE, MASKED, V0, 8>), dim3(nblk), dim3(kThreads), lds, st, a);
-  else
-    hipLaunchKernelGGL((hist5_kernel<MODE, MASKED, V0, 16>), dim3(nblk), dim3(kThreads), lds, st, a);
-}
-
-template <typename K>
-void go(K kern, unsigned nblk, int th, size_t lds, hipStream_t st, const Hist5Args& a) {
-  // blocks above 64 KB of dynamic LDS must opt in (gfx950 has 160 KB per CU)
-  if (lds > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(th), lds, st, a);
-}
-
-template <bool MASKED, int TH>
-void launch5p_t(const Hist5Args& a, int nt_max, unsigned nblk, size_t lds, hipStream_t st) {
-  if (nt_max <= 1) go(hist5p_kernel<MASKED, 1, TH>, nblk, TH, lds, st, a);
-  else if (nt_max <= 2) go(hist5p_kernel<MASKED, 2, TH>, nblk, TH, lds, st, a);
-  else if (nt_max <= 4) go(hist5p_kernel<MASKED, 4, TH>, nblk, TH, lds, st, a);
-  else if (nt_max <= 8) go(hist5p_kernel<MASKED, 8, TH>, nblk, TH, lds, st, a);
-  else go(hist5p_kernel<MASKED, 16, TH>, nblk, TH, lds, st, a);
+// the launch of each kernel family at the instantiation for `masked` and the group's trees-per-group bucket
+template <int MODE, bool V0>
+int launch5(const Hist5Args& a, bool masked, int nt_max, unsigned nblk, size_t lds, hipStream_t st) {
+  return nt_dispatch(nt_max, [&](auto b) {
+    constexpr int NT = decltype(b)::value;
+    return masked ? hist_launch<hist5_kernel<MODE, true, V0, NT>>(nblk, kThreads, lds, st, a)
+                  : hist_launch<hist5_kernel<MODE, false, V0, NT>>(nblk, kThreads, lds, st, a);
+  });
 }
 
 // 1024-thread blocks hold 16384 packed cells (128 KB): one block per CU with
 // the same 16 waves as two 512-thread blocks, but twice the slots per pass.
-template <bool MASKED>
-void launch5p(const Hist5Args& a, int nt_max, unsigned nblk, size_t lds, bool big, hipStream_t st) {
-  if (big) launch5p_t<MASKED, 1024>(a, nt_max, nblk, lds, st);
-  else launch5p_t<MASKED, 512>(a, nt_max, nblk, lds, st);
-}
-
-template <bool MASKED, int TH>
-void launch5q_t(const Hist5Args& a, int nt_max, unsigned nblk, size_t lds, hipStream_t st) {
-  if (nt_max <= 1) go(hist5q_kernel<MASKED, 1, TH>, nblk, TH, lds, st, a);
-  else if (nt_max <= 2) go(hist5q_kernel<MASKED, 2, TH>, nblk, TH, lds, st, a);
-  else if (nt_max <= 4) go(hist5q_kernel<MASKED, 4, TH>, nblk, TH, lds, st, a);
-  else if (nt_max <= 8) go(hist5q_kernel<MASKED, 8, TH>, nblk, TH, lds, st, a);
-  else go(hist5q_kernel<MASKED, 16, TH>, nblk, TH, lds, st, a);
+template <int TH>
+int launch5p_t(const Hist5Args& a, bool masked, int nt_max, unsigned nblk, size_t lds, hipStream_t st) {
+  return nt_dispatch(nt_max, [&](auto b) {
+    constexpr int NT = decltype(b)::value;
+    return masked ? hist_launch<hist5p_kernel<true, NT, TH>>(nblk, TH, lds, st, a)
+                  : hist_launch<hist5p_kernel<false, NT, TH>>(nblk, TH, lds, st, a);
+  });
 }
 
 // compacted kernel: always 1024-thread blocks (16 waves per CU; a 512-thread
 // block at >128 VGPRs would run 8)
-template <bool MASKED>
-void launch5q(const Hist5Args& a, int nt_max, unsigned nblk, size_t lds, hipStream_t st) {
-  launch5q_t<MASKED, 1024>(a, nt_max, nblk, lds, st);
+template <int TH>
+int launch5q_t(const Hist5Args& a, bool masked, int nt_max, unsigned nblk, size_t lds, hipStream_t st) {
+  return nt_dispatch(nt_max, [&](auto b) {
+    constexpr int NT = decltype(b)::value;
+    return masked ? hist_launch<hist5q_kernel<true, NT, TH>>(nblk, TH, lds, st, a)
+                  : hist_launch<hist5q_kernel<false, NT, TH>>(nblk, TH, lds, st, a);
+  });
 }
-
-inline int nt_bucket(int nt) { return nt <= 1 ? 1 : nt <= 2 ? 2 : nt <= 4 ? 4 : nt <= 8 ? 8 : 16; }
 
 }  // namespace
 
@@ -1016,78 +865,36 @@ CDNA_API int cdna_hist5(int mode, const uint64_t* bins, int64_t n, int d, int T,
                         unsigned long long* out, hipStream_t st) {
   if (n <= 0 || S <= 0) return 0;
   Hist5Args a;
-  a.bins = bins;
-  a.n = n;
-  a.d = d;
-  a.T = T;
+  const int rc = hist_fill(a, mode, bins, n, d, T, v0, v1, label, C, build_slot, feat_mask, mask_words, S, B, SB, grp,
+                           ngroups, nchunk, qs0, qs1, out);
+  if (rc != 0) return rc;
   a.codes = codes;
   a.tfirst = tfirst;
-  a.v0 = v0;
-  a.v1 = v1;
-  a.label = label;
-  a.C = C;
-  a.build_slot = build_slot;
-  a.feat_mask = feat_mask;
-  a.mask_words = mask_words;
-  a.S = S;
-  a.B = B;
-  a.SB = SB;
-  const bool classes = (mode & 1) != 0, has_v0 = (mode & 4) != 0;
-  a.K = classes ? C : 2;
-  a.n64 = classes ? 0 : (has_v0 ? 2 : 1);
-  a.n32 = classes ? C : (has_v0 ? 0 : 1);
-  a.grp = grp;
-  a.ngroups = ngroups;
-  a.nchunk = nchunk;
-  a.rows_per_chunk = (n + nchunk - 1) / nchunk;
-  if (a.rows_per_chunk * 255 >= (int64_t)1 << 32) return (int)hipErrorInvalidValue;
-  a.qs0 = qs0;
-  a.qs1 = qs1;
-  a.out = out;
-  const int G = (d + 7) / 8;
+  a.drain_iters = 0;
+  const bool classes = (mode & 1) != 0, has_v0 = (mode & 4) != 0, masked = feat_mask != nullptr;
+  const int ntm = id_span_max;  // carries the max trees per group here
+  if (ntm > kMaxTrees) return (int)hipErrorInvalidValue;
   const size_t plane = (size_t)SB * 8 * B;
-  // id_span_max carries the max trees per group here (local -> slot tables of 256 int16 each)
-  const size_t lds = plane * 8 * a.n64 + ((plane * a.n32 + 3) & ~(size_t)3) * 4 +
-                     (size_t)nt_bucket(id_span_max) * 512 + SB + 16;
-  if (id_span_max > kMaxTrees) return (int)hipErrorInvalidValue;
-  if (lds > 160 * 1024 && !(mode & 16)) return (int)hipErrorInvalidValue;
-  const unsigned nblk = (unsigned)G * ngroups * nchunk;
-  const bool masked = feat_mask != nullptr;
-  const int ntm = id_span_max;
+  const size_t tables = (size_t)nt_bucket(ntm) * 512 + SB + 16;  // local -> slot tables of 256 int16 each, lmask
+  const unsigned nblk = hist_blocks(a);
   if (mode & 16) {  // packed single-atomic regression
     const bool compact = (mode & 64) != 0;
     const bool big = compact || plane > (size_t)kPackCells * 512;
-    {
-      const int th = big ? 1024 : 512;
-      const int64_t rows_ok = ((int64_t)1 << 20) / (wmax > 0 ? wmax + 1 : 1);  // rows * wmax < 2^20
-      a.drain_iters = (int)(rows_ok / th > 0 ? rows_ok / th : 1);
-    }
+    const int th = big ? 1024 : 512;
+    const int64_t rows_ok = ((int64_t)1 << 20) / (wmax > 0 ? wmax + 1 : 1);  // rows * wmax < 2^20
+    a.drain_iters = (int)(rows_ok / th > 0 ? rows_ok / th : 1);
     if (classes || has_v0 || plane > (size_t)kPackCells * 1024) return (int)hipErrorInvalidValue;
     a.n64 = 1;
     a.n32 = 0;
     const size_t rbuf = compact ? (size_t)16 * 128 * 12 : 0;  // per-wave row buffers
-    const size_t lds_p = plane * 8 + rbuf + (size_t)nt_bucket(ntm) * 512 + SB + 16;
-    if (lds_p > 160 * 1024) return (int)hipErrorInvalidValue;
-    if (compact) {
-      if (masked) launch5q<true>(a, ntm, nblk, lds_p, st);
-      else launch5q<false>(a, ntm, nblk, lds_p, st);
-    } else {
-      if (masked) launch5p<true>(a, ntm, nblk, lds_p, big, st);
-      else launch5p<false>(a, ntm, nblk, lds_p, big, st);
-    }
-    return (int)hipGetLastError();
+    const size_t lds_p = plane * 8 + rbuf + tables;
+    if (compact) return launch5q_t<1024>(a, masked, ntm, nblk, lds_p, st);
+    return big ? launch5p_t<1024>(a, masked, ntm, nblk, lds_p, st) : launch5p_t<512>(a, masked, ntm, nblk, lds_p, st);
   }
-  if (classes) {
-    if (masked) launch5<1, true, false>(a, ntm, nblk, lds, st);
-    else launch5<1, false, false>(a, ntm, nblk, lds, st);
-  } else if (has_v0) {
-    if (masked) launch5<0, true, true>(a, ntm, nblk, lds, st);
-    else launch5<0, false, true>(a, ntm, nblk, lds, st);
-  } else {
-    if (masked) launch5<0, true, false>(a, ntm, nblk, lds, st);
-    else launch5<0, false, false>(a, ntm, nblk, lds, st);
-  }
-  return (int)hipGetLastError();
+  const size_t lds = hist_plane_bytes(a) + tables;
+  if (classes) return launch5<1, false>(a, masked, ntm, nblk, lds, st);
+  if (has_v0) return launch5<0, true>(a, masked, ntm, nblk, lds, st);
+  return launch5<0, false>(a, masked, ntm, nblk, lds, st);
 }
 
 // Blocks of a partition7 launch over n rows.

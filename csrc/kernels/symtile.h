@@ -132,17 +132,6 @@ __device__ __forceinline__ void reduce_slabs(double (&red)[16][16], const S* __r
   }
 }
 
-// Dynamic LDS above the 64 KB default: raised to `bytes` (the kernel's widest plan) once per kernel instantiation
-// (`raised`: its static bool[64]) and device.
-inline int raise_lds(const void* fn, bool* raised, size_t bytes) {
-  int dev = 0;
-  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && raised[dev]) return 0;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return (int)e;
-  if (dev >= 0 && dev < 64) raised[dev] = true;
-  return 0;
-}
-
 // rows of X addressable as float4: what the VW = 4 kernels need
 inline bool float4_rows(const float* X, int d, int64_t ldx) {
   return d % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
