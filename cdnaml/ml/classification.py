@@ -1,4 +1,6 @@
 from ..models.classification import (DecisionTreeClassificationModel, DecisionTreeClassifier,  # noqa: F401
                                      GBTClassificationModel, GBTClassifier, LinearSVC, LinearSVCModel,
-                                     LogisticRegression, LogisticRegressionModel, NaiveBayes, NaiveBayesModel,
+                                     LogisticRegression, LogisticRegressionModel,
+                                     MultilayerPerceptronClassificationModel, MultilayerPerceptronClassifier,
+                                     NaiveBayes, NaiveBayesModel,
                                      RandomForestClassificationModel, RandomForestClassifier)

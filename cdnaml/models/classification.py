@@ -5,7 +5,9 @@ the fused K11 HIP kernel (margin, log-loss and gradient together) plus one
 RCCL all-reduce of d+2 doubles; its margins are fp64 (Spark's Double).  Multinomial uses fp64 GEMMs at course
 sizes, fp32 device GEMMs above MULTINOMIAL_F64_MAX.  Tree
 classifiers (DT / RF / GBT) share the histogram engine with class-count
-statistics (gini / entropy).  Reference: MLE 03 - Logistic Regression
+statistics (gini / entropy).  MultilayerPerceptronClassifier: every L-BFGS evaluation is one pass of the fused
+K24 kernel (forward, softmax cross-entropy, backward and weight gradients on the fp32 MFMA) plus one all-reduce of
+P + 1 doubles.  Reference: MLE 03 - Logistic Regression
 Lab.py:99-158; Labs/ML 07L:42-209 (RandomForestClassifier + AUC).
 """
 from __future__ import annotations
@@ -24,8 +26,8 @@ from .base import Estimator, Model
 from .linalg import DenseMatrix, DenseVector
 from .optim import minimize
 from .param import NO_DEFAULT, TypeConverters as TC, keyword_init
-from .regression import (_GBT, _PRED, _RF, _TREE, _TreeModelBase, _bag_weights, _combine_weights, _num_classes,
-                         _subforest, resolve_subset, tree_fit_prepare)
+from .regression import (_GBT, _PRED, _RF, _TREE, _TreeModelBase, _bag_weights, _combine_weights, _default_seed,
+                         _num_classes, _subforest, resolve_subset, tree_fit_prepare)
 from .tree.engine import ForestTrainer, TreeParams
 from .tree.forest import Forest
 from .util import VECTOR_F64_MAX, IllegalArgumentException, centered_gram, local_batch, local_xyw, require_vector
@@ -353,6 +355,200 @@ class _LogRegTrainingSummary(_LogRegSummary):
         super().__init__(model, dataset)
         self.objectiveHistory = hist
         self.totalIterations = iters
+
+
+# ========================================================= MultilayerPerceptronClassifier
+def _to_weight_list(v):
+    """``initialWeights``: a Vector, an array or None -> a list of floats (what the params persist as)."""
+    if v is None:
+        return None
+    return [float(x) for x in np.asarray(v.toArray() if hasattr(v, "toArray") else v, dtype=np.float64).reshape(-1)]
+
+
+_MLP_PARAMS = dict(_CLS, **{
+    "layers": ("Sizes of layers from input layer to output layer E.g., Array(780, 100, 10) means 780 inputs, one "
+               "hidden layer with 100 neurons and output layer of 10 neurons.", None, TC.toListInt),
+    "maxIter": ("max number of iterations (>= 0)", 100, TC.toInt),
+    "tol": ("the convergence tolerance for iterative algorithms (>= 0)", 1e-6, TC.toFloat),
+    "seed": ("random seed", None, TC.toInt),
+    "blockSize": ("Block size for stacking input data in matrices. Data is stacked within partitions.", 128,
+                  TC.toInt),
+    "solver": ("The solver algorithm for optimization. Supported options: l-bfgs, gd.", "l-bfgs", TC.toString),
+    "stepSize": ("Step size to be used for each iteration of optimization (>= 0).", 0.03, TC.toFloat),
+    "initialWeights": ("The initial weights of the model.", None, _to_weight_list),
+})
+
+MLP_INIT_STREAM = 24   # Philox stream of the initial weight draws
+
+
+def mlp_initial_weights(layers, seed: int) -> np.ndarray:
+    """Spark's scheme in Spark's flat layout: W_l ~ U(-b, b) with b = sqrt(6 / (numIn + numOut)), biases 0.  The
+    uniforms are the project's Philox keyed by ``seed``, one per position of the flat vector (a bias position's draw
+    is unused), so the vector does not depend on the device or on the number of ranks."""
+    from ..ops import philox
+    P = K.mlp_num_params(layers)
+    u = philox.uniform(P, seed, 0, MLP_INIT_STREAM)
+    theta, off = np.zeros(P), 0
+    for i, o in zip(layers[:-1], layers[1:]):
+        b = math.sqrt(6.0 / (i + o))
+        theta[off:off + o * i] = (2.0 * u[off:off + o * i] - 1.0) * b
+        off += o * i + o
+    return theta
+
+
+class MultilayerPerceptronClassifier(Estimator):
+    """``pyspark.ml.classification.MultilayerPerceptronClassifier``: one affine layer per consecutive pair of
+    ``layers``, sigmoid after every affine layer but the last, softmax with cross-entropy on top, fitted by L-BFGS.
+    ``model.weights`` and ``initialWeights`` are Spark's flat vector (per layer W column-major, then the biases) and
+    interchangeable with Spark's.
+
+    Every objective evaluation is one pass of the K24 ``mlp_step`` op over the local rows plus one all-reduce of
+    P + 1 doubles.  Two things differ from Spark by construction.  The initial weights follow Spark's distribution
+    but are drawn with this project's Philox generator: Spark's come from its JVM generator and cannot be
+    reproduced, so ``initialWeights`` is the route to parity.  The objective is the plain mean over the rows of
+    logsumexp(z) - z[label]; Spark averages within each stacked block of ``blockSize`` rows and then over the
+    blocks, which weighs the rows of a short last block differently (``blockSize`` is accepted and otherwise
+    unused: it only batches Spark's JVM GEMMs).  ``solver="gd"`` is not implemented."""
+    _params = _MLP_PARAMS
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        keyword_init(self, kwargs)
+
+    def _fit(self, dataset):
+        layers = self.getLayers()
+        if layers is None or len(layers) < 2 or min(layers) < 1:
+            raise IllegalArgumentException(f"MultilayerPerceptronClassifier layers must hold at least 2 positive "
+                                           f"sizes (input and output), got {layers}")
+        if self.getSolver() == "gd":
+            raise NotImplementedError("MultilayerPerceptronClassifier: solver='gd' (Spark's minibatch gradient "
+                                      "descent) is not implemented; use solver='l-bfgs'")
+        if self.getSolver() != "l-bfgs":
+            raise IllegalArgumentException(f"MultilayerPerceptronClassifier solver must be l-bfgs or gd, got "
+                                           f"{self.getSolver()}")
+        fc, lc = self.getFeaturesCol(), self.getLabelCol()
+        X, y, _ = local_xyw(dataset, fc, lc, None, keep_f64=True)
+        session = dataset._session
+        comm = session.comm
+        d, C = layers[0], layers[-1]
+        n = X.shape[0]
+        if n == 0:
+            X = torch.zeros((0, d), dtype=X.dtype, device=X.device)
+        # the checks are global: every rank raises, or none does
+        odd = float(((y != torch.floor(y)) | (y < 0)).sum()) if n else 0.0
+        chk = torch.tensor([float(n), float(X.shape[1] != d), odd], dtype=torch.float64, device=comm.device)
+        comm.all_reduce(chk)
+        mx = torch.tensor([float(y.max()) if n else 0.0], dtype=torch.float64, device=comm.device)
+        comm.all_reduce(mx, "max")
+        n_glob = float(chk[0])
+        if float(chk[1]) > 0:
+            raise IllegalArgumentException(f"requirement failed: The input layer size layers[0] = {d} does not match "
+                                           f"the size {X.shape[1]} of the vectors in column {fc}.")
+        if float(chk[2]) > 0:
+            raise IllegalArgumentException(f"requirement failed: Classifier found {int(chk[2])} labels that are not "
+                                           f"non-negative integers in column {lc}.")
+        if float(mx) >= C:
+            raise IllegalArgumentException(f"requirement failed: Classifier found max label value = {float(mx)} in "
+                                           f"column {lc}, but the output layer has layers[-1] = {C} neurons: labels "
+                                           f"must be in [0, {C}).")
+        P = K.mlp_num_params(layers)
+        init = self.getInitialWeights()
+        if init is not None:
+            if len(init) != P:
+                raise IllegalArgumentException(f"requirement failed: initialWeights has {len(init)} entries, layers "
+                                               f"{layers} need {P}.")
+            theta0 = np.asarray(init, dtype=np.float64)
+        else:
+            seed = self.getSeed() if self.getSeed() is not None else _default_seed(type(self))
+            theta0 = mlp_initial_weights(layers, seed)
+        yi = y.to(torch.int32)
+
+        def fg(theta):
+            loss, g = K.mlp_step(X, yi, theta, layers, K.MLP_STEP)
+            acc = torch.cat([g, loss.reshape(1)])
+            comm.all_reduce(acc)
+            a = acc.cpu().numpy() / max(n_glob, 1.0)
+            return float(a[P]), a[:P].copy()
+        theta, hist, iters = minimize(fg, theta0, self.getMaxIter(), self.getTol())
+        model = MultilayerPerceptronClassificationModel(theta, layers)
+        model._post_fit(self)
+        model.summary = _LogRegTrainingSummary(model, dataset, hist, iters)
+        return model
+
+
+class MultilayerPerceptronClassificationModel(Model):
+    _params = _MLP_PARAMS
+
+    def __init__(self, weights=None, layers=None):
+        super().__init__()
+        self._layers = [int(v) for v in layers] if layers is not None else [0, 0]
+        self._theta = np.asarray(weights.toArray() if hasattr(weights, "toArray") else
+                                 (weights if weights is not None else np.zeros(0)), dtype=np.float64).reshape(-1)
+        if layers is not None:
+            keyword_init(self, {"layers": self._layers})   # ``layers`` is a Param, as in Spark 3: getLayers() reads it
+        self.summary = None
+
+    @property
+    def weights(self):
+        return DenseVector(self._theta)
+
+    @property
+    def numFeatures(self):
+        return self._layers[0]
+
+    @property
+    def numClasses(self):
+        return self._layers[-1]
+
+    @property
+    def hasSummary(self):
+        return self.summary is not None
+
+    def _one(self, features):
+        x = np.asarray(features.toArray() if hasattr(features, "toArray") else features, dtype=np.float64)
+        return K.mlp_step(torch.from_numpy(x.reshape(1, -1).copy()), None, self._theta, self._layers, K.MLP_PREDICT)
+
+    def predictRaw(self, features):
+        return DenseVector(self._one(features)[0][0].numpy())
+
+    def predictProbability(self, features):
+        return DenseVector(self._one(features)[1][0].numpy())
+
+    def predict(self, features):
+        raw, prob, pred = self._one(features)
+        thresholds = self.getThresholds()
+        return float(_argmax_with_thresholds(prob, thresholds)[0]) if thresholds else float(pred[0])
+
+    def _transform(self, dataset):
+        fc = self.getFeaturesCol()
+        require_vector(dataset, fc)
+        names = (self.getRawPredictionCol(), self.getPredictionCol(), self.getProbabilityCol())
+        layers, thresholds = self._layers, self.getThresholds()
+        prep = K.MlpPrepared(self._theta, layers)   # the device tables are built once, not per batch
+
+        def fn(b, ctx):
+            X = b.columns[fc].values
+            if X.shape[0] == 0:
+                z = torch.zeros((0, layers[-1]), dtype=torch.float64, device=X.device)
+                return _append_cls_outputs(b, z, z, z[:, 0], names)
+            X = X if X.dtype == torch.float64 and X.numel() <= VECTOR_F64_MAX else X.float()
+            raw, prob, pred = K.mlp_step(X, None, self._theta, layers, K.MLP_PREDICT, prepared=prep)
+            if thresholds:
+                pred = _argmax_with_thresholds(prob, thresholds)
+            return _append_cls_outputs(b, raw, prob, pred, names)
+        return dataset._new(MapPlan(dataset._plan, "MultilayerPerceptronClassificationModel", fn))
+
+    def evaluate(self, dataset):
+        return _LogRegSummary(self, dataset)
+
+    def _save_state(self):
+        return {"layers": list(self._layers)}, {"weights": torch.tensor(self._theta)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._theta = tensors["weights"].numpy()
+        self._layers = [int(v) for v in extra["layers"]]
+        keyword_init(self, {"layers": self._layers})
+        self.summary = None
 
 
 # ========================================================= tree classifiers

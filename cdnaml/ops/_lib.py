@@ -241,6 +241,11 @@ _SIGS = {
     "cdna_gmm_step_workspace": ([c_int64, c_int, c_int], c_int64),
     "cdna_gmm_step": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_mlp_plan": ([c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p], c_int),
+    "cdna_mlp_table_offsets": ([c_void_p, c_int, c_void_p], c_int),
+    "cdna_mlp_step_workspace": ([c_int64, c_void_p, c_int], c_int64),
+    "cdna_mlp_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                       c_void_p, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

@@ -1971,6 +1971,195 @@ def gmm_step(X: torch.Tensor, w: Optional[torch.Tensor], mu: torch.Tensor, A: to
     return stats
 
 
+# ------------------------------------------------------------ K24 mlp_step (mlp.hip)
+MLP_STEP, MLP_PREDICT = 0, 1
+MLP_MAX_WIDTH = 128        # the fused kernel's range: every layer width, the input's d included, <= 128
+MLP_MAX_LAYERS = 3         # at most 3 affine layers (two hidden), i.e. len(layers) <= 4; and 2 <= classes
+MLP_HOST_CHUNK = 1 << 18   # rows per pass of the host formulation (bounds its [rows, width] intermediates)
+
+
+def mlp_num_params(layers) -> int:
+    return sum(o * i + o for i, o in zip(layers[:-1], layers[1:]))
+
+
+def mlp_unpack(theta: torch.Tensor, layers):
+    """[(W [out, in], b [out])] per affine layer from Spark's flat vector: per layer W column-major (entry (o, i) at
+    off + o + i * out), then the out biases."""
+    out, off = [], 0
+    for i, o in zip(layers[:-1], layers[1:]):
+        out.append((theta[off:off + o * i].reshape(i, o).T, theta[off + o * i:off + o * i + o]))
+        off += o * i + o
+    return out
+
+
+class MlpPrepared:
+    """The weights of one net as ``mlp_step`` consumes them, prepared once per (device, row dtype, path) and reused
+    by every call that is given this object: an objective evaluation's STEP, a model's PREDICT per batch."""
+
+    def __init__(self, theta, layers):
+        self.layers = [int(v) for v in layers]
+        self.theta = torch.as_tensor(theta, dtype=torch.float64).reshape(-1).cpu()
+        if self.theta.numel() != mlp_num_params(self.layers):
+            raise ValueError(f"mlp_step: {self.theta.numel()} weights for layers {self.layers}, expected "
+                             f"{mlp_num_params(self.layers)}")
+        self._made = {}
+
+    def on(self, dev, f32: bool, native: bool):
+        """[(W, b)] fp64 on ``dev`` (the weights rounded to fp32 first for fp32 rows); for the native path the
+        kernel's table: per layer the zero-padded fp32 W^T [in up to 2][out up to 32], W [out up to 2][in up to 32]
+        and b [out up to 32]."""
+        key = (str(dev), f32, native)
+        if key not in self._made:
+            th = self.theta.float().double() if f32 else self.theta
+            Wb = mlp_unpack(th, self.layers)
+            if native:
+                L = _lib.lib()
+                lay = np.asarray(self.layers, dtype=np.int32)
+                plan = np.zeros(8, dtype=np.int64)
+                off = np.zeros(3 * (len(lay) - 1), dtype=np.int64)
+                _lib.check(L.cdna_mlp_plan(None, 1, int(lay[0]), lay.ctypes.data, len(lay), plan.ctypes.data),
+                           "cdna_mlp_plan")
+                _lib.check(L.cdna_mlp_table_offsets(lay.ctypes.data, len(lay), off.ctypes.data),
+                           "cdna_mlp_table_offsets")
+                tab = np.zeros(int(plan[7]), dtype=np.float32)
+                r2, r32 = (lambda v: (v + 1) // 2 * 2), (lambda v: (v + 31) // 32 * 32)
+                for l, (W, b) in enumerate(Wb):
+                    o, i = W.shape
+                    W32 = W.numpy().astype(np.float32)
+                    tab[off[3 * l]:off[3 * l] + r2(i) * r32(o)].reshape(r2(i), r32(o))[:i, :o] = W32.T
+                    tab[off[3 * l + 1]:off[3 * l + 1] + r2(o) * r32(i)].reshape(r2(o), r32(i))[:o, :i] = W32
+                    tab[off[3 * l + 2]:off[3 * l + 2] + o] = b.numpy().astype(np.float32)
+                self._made[key] = upload(dev, tab)[0]
+            else:
+                self._made[key] = [(W.to(dev).contiguous(), b.to(dev)) for W, b in Wb]
+        return self._made[key]
+
+
+def _mlp_native_plan(X: torch.Tensor, layers):
+    """cdna_mlp_plan's answer for these operands (None: the host formulation) and X as the kernel takes it."""
+    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] != layers[0]:
+        return None, X
+    X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
+    lay = np.asarray(layers, dtype=np.int32)
+    out = np.zeros(8, dtype=np.int64)
+    _lib.check(_lib.lib().cdna_mlp_plan(_ptr(X), X.shape[0], X.stride(0), lay.ctypes.data, len(lay),
+                                        out.ctypes.data), "cdna_mlp_plan")
+    return (out if out[0] else None), X
+
+
+def mlp_plan(X: torch.Tensor, layers) -> Dict[str, object]:
+    """What :func:`mlp_step` runs for these operands, from the dispatch's own host function (nothing is launched):
+    ``path`` "native" or "host"; for the native path ``slots`` (gradient tiles per wave of the STEP instantiation:
+    1, 3, 6 or 12), ``vw`` (4: float4 row loads, 1: scalar loads), ``nblk``, ``rows_per_block``, ``tiles`` (32 x 32
+    gradient tiles over all layers) and ``lds`` (bytes per block)."""
+    layers = [int(v) for v in layers]
+    out, _ = _mlp_native_plan(X, layers)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "slots": int(out[1]), "vw": int(out[2]), "nblk": int(out[3]),
+            "rows_per_block": int(out[4]), "tiles": int(out[5]), "lds": int(out[6])}
+
+
+def _first_argmax(Z: torch.Tensor) -> torch.Tensor:
+    """argmax over dim 1, the lowest index among equals, int32."""
+    C = Z.shape[1]
+    idx = torch.arange(C, device=Z.device).expand_as(Z)
+    return torch.where(Z == Z.max(1, keepdim=True).values, idx, torch.full_like(idx, C)).min(1).values \
+        .clamp_max(C - 1).to(torch.int32)
+
+
+def mlp_step(X: torch.Tensor, y: Optional[torch.Tensor], theta32, layers, mode: int = MLP_STEP, native: bool = True,
+             prepared: Optional[MlpPrepared] = None):
+    """Loss and gradient sums, or the predictions, of a multilayer perceptron over the local rows.
+
+    X [n, layers[0]] fp32 or fp64, y [n] integer labels in [0, layers[-1]) (STEP only), ``theta32`` the flat weight
+    vector in Spark's layout (see ``mlp_unpack``).  The net: one affine layer per consecutive pair of ``layers``,
+    sigmoid after every layer but the last, softmax with cross-entropy on top.
+
+    MLP_STEP returns (loss_sum fp64 scalar, grad_sum fp64 [P]): the sums over the rows of logsumexp(z) - z[label]
+    and of its gradient in the flat layout, un-normalised.  MLP_PREDICT returns (raw [n, C] fp64, prob [n, C] fp64,
+    pred [n] int32): the last affine layer's output, its softmax and the argmax of raw, the lowest index among
+    equals.
+
+    For fp32 X the op is defined at the weights rounded to fp32, on the device and in the host formulation alike;
+    fp64 X uses them as they are.  fp32 X on a GPU with every width <= MLP_MAX_WIDTH, at most MLP_MAX_LAYERS affine
+    layers and at least 2 classes (any n >= 1, row stride and alignment) runs the K24 kernel: every matmul on the
+    exact-fp32 MFMA, fp32 sigmoid, the softmax, the loss and the delta of the top layer in fp64, per-block partial
+    sums reduced in a fixed order (two calls on the same input return the same bits).  Everything else takes the
+    host formulation: a plain forward / explicit backward in fp64 torch ops, MLP_HOST_CHUNK rows at a time
+    (``native=False`` asks for it inside the range too: bench/mlp_micro.py times the two side by side).
+    ``prepared``: a MlpPrepared of the same weights, so that repeated calls build the device tables once.
+    """
+    layers = [int(v) for v in layers]
+    n = X.shape[0]
+    C = layers[-1]
+    dev = X.device
+    if X.dim() != 2 or X.shape[1] != layers[0]:
+        raise ValueError(f"mlp_step: X has {X.shape[1]} columns, layers[0] is {layers[0]}")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    f32 = X.dtype == torch.float32
+    prep = prepared if prepared is not None else MlpPrepared(theta32, layers)
+    if prep.layers != layers:
+        raise ValueError(f"mlp_step: prepared for layers {prep.layers}, called with {layers}")
+    P = prep.theta.numel()
+    plan, Xn = _mlp_native_plan(X, layers) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        lay = np.asarray(layers, dtype=np.int32)
+        tab = prep.on(dev, True, True)
+        out = ws = raw = prob = pred = yi = None
+        if mode == MLP_STEP:
+            yi = y.to(device=dev, dtype=torch.int32).contiguous()
+            # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+            out = torch.empty(P + 1, dtype=torch.float64, device=dev)
+            ws = torch.empty(L.cdna_mlp_step_workspace(n, lay.ctypes.data, len(lay)), dtype=torch.float64, device=dev)
+        else:
+            raw = torch.empty((n, C), dtype=torch.float64, device=dev)
+            prob = torch.empty((n, C), dtype=torch.float64, device=dev)
+            pred = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(L.cdna_mlp_step(_ptr(Xn), n, Xn.stride(0), _ptr(yi), _ptr(tab), lay.ctypes.data, len(lay),
+                                   int(mode), _ptr(out), _ptr(ws), _ptr(raw), _ptr(prob), _ptr(pred), _stream(dev)),
+                   "cdna_mlp_step")
+        return (out[P], out[:P]) if mode == MLP_STEP else (raw, prob, pred)
+    # host formulation, MLP_HOST_CHUNK rows at a time
+    Wb = prep.on(dev, f32, False)
+    nl = len(Wb)
+    loss = torch.zeros((), dtype=torch.float64, device=dev)
+    gW = [torch.zeros_like(W) for W, _ in Wb]
+    gb = [torch.zeros_like(b) for _, b in Wb]
+    raws, probs, preds = [], [], []
+    yl = None if y is None else y.to(device=dev, dtype=torch.int64)
+    for i0 in range(0, n, MLP_HOST_CHUNK):
+        acts = [X[i0:i0 + MLP_HOST_CHUNK].double()]
+        for l, (W, b) in enumerate(Wb):
+            Z = acts[-1] @ W.T + b
+            acts.append(torch.sigmoid(Z) if l < nl - 1 else Z)
+        Z = acts[-1]
+        lse = torch.logsumexp(Z, 1)
+        Pm = torch.exp(Z - lse[:, None])
+        if mode == MLP_PREDICT:
+            raws.append(Z)
+            probs.append(Pm)
+            preds.append(_first_argmax(Z))
+            continue
+        yc = yl[i0:i0 + MLP_HOST_CHUNK]
+        loss += (lse - Z.gather(1, yc[:, None])[:, 0]).sum()
+        D = Pm
+        D.scatter_add_(1, yc[:, None], torch.full((yc.shape[0], 1), -1.0, dtype=torch.float64, device=dev))
+        for l in range(nl - 1, -1, -1):
+            gW[l] += D.T @ acts[l]
+            gb[l] += D.sum(0)
+            if l > 0:
+                D = (D @ Wb[l][0]) * (acts[l] * (1.0 - acts[l]))
+    if mode == MLP_PREDICT:
+        if not raws:
+            z = torch.zeros((0, C), dtype=torch.float64, device=dev)
+            return z, z.clone(), torch.zeros(0, dtype=torch.int32, device=dev)
+        return torch.cat(raws), torch.cat(probs), torch.cat(preds)
+    return loss, torch.cat([t for W, b in zip(gW, gb) for t in (W.T.reshape(-1), b)])
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
