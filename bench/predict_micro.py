@@ -33,6 +33,21 @@ def complete_forest(T, depth, d, seed=0):
             torch.tensor(vals, dtype=torch.float32))
 
 
+def report(label, reps, n, d, call):
+    """One warm-up call, then every repeat timed on its own: the median, and the repeats' spread."""
+    call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    med = float(np.median(ms))
+    print(f"{label} {med:7.3f} ms (min {min(ms):.3f}, max {max(ms):.3f} of {reps})  {n / med / 1e6:.3f}e9 rows/s  "
+          f"{n * d * 4 / med / 1e9:.2f} TB/s of X", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=float, default=1e8)
@@ -49,35 +64,20 @@ def main():
         nodes, roots, vals = nodes.to(dev), roots.to(dev), vals.to(dev)
         tw = torch.full((T,), 1.0 / T, device=dev)
         masks = torch.zeros(8, dtype=torch.int32, device=dev)
-        K.tree_predict(X, nodes, roots, tw, vals, masks, 1, None)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(a.reps):
-            K.tree_predict(X, nodes, roots, tw, vals, masks, 1, None)
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) / a.reps * 1e3
-        print(f"T={T:3d} depth={a.depth} int4 nodes: {ms:7.2f} ms  {n / ms / 1e6:.3f}e9 rows/s  "
-              f"{n * d * 4 / ms / 1e9:.2f} TB/s of X", flush=True)
+        report(f"T={T:3d} depth={a.depth} int4 nodes:", a.reps, n, d,
+               lambda: K.tree_predict(X, nodes, roots, tw, vals, masks, 1, None))
         # heap layout: the complete trees above are already in heap order per tree
         S = 2 ** (a.depth + 1) - 1
         nh = nodes.cpu().numpy().reshape(T, S, 4)
-        heap = np.stack([nh[..., 0], nh[..., 1]], -1).astype(np.int32)
         leaf = nh[..., 0] < 0
-        vh = vals.cpu().numpy()
-        heap[..., 1][leaf] = vh[nh[..., 1][leaf]].astype(np.float32).view(np.int32)
-        heap_t = torch.from_numpy(heap).to(dev)
+        hv = np.zeros((T, S), dtype=np.float64)
+        hv[leaf] = vals.cpu().numpy().astype(np.float64)[nh[..., 1][leaf]]
+        heap_t = torch.from_numpy(K.pack_heap(np.ascontiguousarray(nh[..., :2]), hv, a.depth)).to(dev)
         ref = K.tree_predict(X[:100000], nodes, roots, tw, vals, masks, 1, None)
         got = K.tree_predict_heap(X[:100000], heap_t, a.depth, tw, masks)
-        assert torch.allclose(ref, got, atol=1e-5), "heap predict mismatch"
-        K.tree_predict_heap(X, heap_t, a.depth, tw, masks)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(a.reps):
-            K.tree_predict_heap(X, heap_t, a.depth, tw, masks)
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) / a.reps * 1e3
-        print(f"T={T:3d} depth={a.depth} heap:       {ms:7.2f} ms  {n / ms / 1e6:.3f}e9 rows/s  "
-              f"{n * d * 4 / ms / 1e9:.2f} TB/s of X", flush=True)
+        assert got is not None and torch.equal(ref, got), "heap predict mismatch"
+        report(f"T={T:3d} depth={a.depth} heap:      ", a.reps, n, d,
+               lambda: K.tree_predict_heap(X, heap_t, a.depth, tw, masks))
 
 
 if __name__ == "__main__":

@@ -190,6 +190,8 @@ _SIGS = {
                         c_void_p], c_int),
     "cdna_tree_predict": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p,
                            c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p], c_int),
+    "cdna_tree_predict_plan": ([c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int64, c_void_p], c_int),
+    "cdna_tree_predict_heap_plan": ([c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_int, c_void_p], c_int),
     "cdna_heap_last_level": ([c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double,
                               c_double, c_void_p, c_int, c_int, c_void_p], c_int),
     "cdna_tree_predict_heap": ([c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p,

@@ -412,7 +412,8 @@ def binize(X: torch.Tensor, thr: torch.Tensor, nthr: torch.Tensor, missing: Opti
         nt = int(nthr[f])
         x = Xf[:, f]
         if nt < 0:
-            b = torch.clamp(x.to(torch.int64), 0, 255)
+            # clamped in float first: the conversion of NaN, +-inf and values past int64 is not defined
+            b = torch.clamp(torch.nan_to_num(x, nan=0.0), 0.0, 255.0).to(torch.int64)
         else:
             b = torch.searchsorted(thr[f, :nt].float().contiguous(), x.contiguous(), right=False)
             b = torch.where(torch.isnan(x), torch.full_like(b, nt), b)
@@ -1102,6 +1103,56 @@ BINIZE_RESIDENT = False
 PREDICT_RESIDENT = False
 
 
+PREDICT_STAGING = ("scalar", "float4", "float4+prefetch")  # trees.hip kStage*: how a 64-row X tile reaches LDS
+
+
+def _predict_rows(X: torch.Tensor) -> torch.Tensor:
+    """The fp32 rows (unit column stride) whose pointer the raw-feature predict kernels are called with."""
+    X = X.float()
+    return X if X.stride(1) == 1 else X.contiguous()
+
+
+def tree_predict_plan(X: torch.Tensor, n_nodes: int, T: int, K: int, n_values: int) -> Dict[str, object]:
+    """What :func:`tree_predict` launches for these device rows and a forest of ``n_nodes`` nodes, ``T`` trees and
+    ``n_values`` leaf values, from the launcher's own host function (nothing is launched): ``staging`` (one of
+    PREDICT_STAGING), ``n_nodes_lds`` / ``n_vals_lds`` (nodes / leaf values copied into LDS; 0: read from global
+    memory), ``grid`` and ``lds_bytes``."""
+    assert _native(X)
+    X = _predict_rows(X)
+    n, d = X.shape
+    out = np.zeros(5, dtype=np.int32)
+    _lib.check(_lib.lib().cdna_tree_predict_plan(_ptr(X), n, d, X.stride(0), int(n_nodes), int(T), int(K),
+                                                 int(n_values), out.ctypes.data), "cdna_tree_predict_plan")
+    stage, nn, nv, grid, lds = (int(v) for v in out)
+    return {"staging": PREDICT_STAGING[stage], "n_nodes_lds": nn, "n_vals_lds": nv, "grid": grid, "lds_bytes": lds}
+
+
+def tree_predict_heap_plan(X: torch.Tensor, depth: int, T: int) -> Dict[str, object]:
+    """What :func:`tree_predict_heap` launches for these device rows and ``T`` trees of depth ``depth`` (the
+    launcher's own host function; nothing is launched): ``fits`` (False: over the LDS budget, the call returns
+    None), ``lds_bytes``, ``staging``, ``grid`` and ``grid_resident`` (the blocks with PREDICT_RESIDENT off / on;
+    the latter 0 when the forest does not fit)."""
+    assert _native(X)
+    X = _predict_rows(X)
+    n, d = X.shape
+    out = np.zeros(8, dtype=np.int32)
+    _lib.check(_lib.lib().cdna_tree_predict_heap_plan(_ptr(X), n, d, X.stride(0), int(depth), int(T), 0,
+                                                      out.ctypes.data), "cdna_tree_predict_heap_plan")
+    return {"fits": bool(out[0]), "lds_bytes": int(out[1]), "staging": PREDICT_STAGING[int(out[2])],
+            "grid": int(out[3]), "grid_resident": int(out[4])}
+
+
+def tree_predict_heap_binned_plan(n: int, G: int, d: int, depth: int, T: int) -> Dict[str, object]:
+    """What :func:`tree_predict_heap_binned` launches on a device (the launcher's own host function; nothing is
+    launched): ``fits``, ``lds_bytes``, ``nt`` (trees per wave and pass: the kernel's template argument),
+    ``passes`` (over a wave's trees), ``prefetch`` (the next tile's words held in registers) and ``grid``."""
+    out = np.zeros(8, dtype=np.int32)
+    _lib.check(_lib.lib().cdna_tree_predict_heap_plan(None, int(n), int(d), 0, int(depth), int(T), int(G),
+                                                      out.ctypes.data), "cdna_tree_predict_heap_plan")
+    return {"fits": bool(out[0]), "lds_bytes": int(out[1]), "nt": int(out[5]), "passes": int(out[6]),
+            "prefetch": bool(out[2]), "grid": int(out[3])}
+
+
 def tree_predict_heap(X: torch.Tensor, heap: torch.Tensor, depth: int, tree_w: torch.Tensor,
                       masks: torch.Tensor, base: float = 0.0, dtype=torch.float64) -> Optional[torch.Tensor]:
     """Single-output ensemble prediction over a packed heap forest (int32 [T, 2^(depth+2)-2], ``pack_heap``):
@@ -1113,8 +1164,7 @@ def tree_predict_heap(X: torch.Tensor, heap: torch.Tensor, depth: int, tree_w: t
         return None
     assert heap.dtype == torch.int32 and heap.dim() == 2 and heap.shape[1] == (4 << depth) - 2, \
         (tuple(heap.shape), depth)
-    X = X.float()
-    X = X if X.stride(1) == 1 else X.contiguous()
+    X = _predict_rows(X)
     out = torch.empty((n, 1), dtype=dtype, device=X.device)
     if n == 0:
         return out
@@ -1216,8 +1266,7 @@ def tree_predict(X: torch.Tensor, nodes: torch.Tensor, roots: torch.Tensor, tree
     n, d = X.shape
     T = roots.numel()
     if _native(X):
-        X = X.float()
-        X = X if X.stride(1) == 1 else X.contiguous()
+        X = _predict_rows(X)
         out = torch.empty((n, K), dtype=torch.float64, device=X.device)
         if n:
             m = masks.int().contiguous() if masks.numel() else torch.zeros(8, dtype=torch.int32, device=X.device)
@@ -1246,12 +1295,11 @@ def tree_predict(X: torch.Tensor, nodes: torch.Tensor, roots: torch.Tensor, tree
 def _raw_left(x: torch.Tensor, f: torch.Tensor, payload: torch.Tensor, mk: torch.Tensor) -> torch.Tensor:
     """The predictors' decision on raw fp32 values ``x`` for packed node codes ``f`` (trees.hip): numeric (f >= 0)
     left iff x <= the fp32 threshold whose bits are ``payload`` (NaN goes right); categorical (f <= -2) left iff
-    the bit (int)x of the mask at offset ``payload`` is set, out of [0, 256) goes right."""
+    the bit (int)x of the mask at offset ``payload`` is set; (int)x out of [0, 256) and NaN go right."""
     cont = f >= 0
     thr = payload.to(torch.int32).view(torch.float32)
-    c = x.to(torch.int64)
-    okc = (c >= 0) & (c < 256)
-    cc = c.clamp(0, 255)
+    okc = (x > -1) & (x < 256)  # (int)x in [0, 256), decided in float: false for NaN, +-inf and huge values
+    cc = torch.where(okc, x, torch.zeros_like(x)).to(torch.int64)
     moff = torch.where(f <= -2, payload, torch.zeros_like(payload)).clamp(min=0)
     words = mk[(moff * 8 + (cc >> 5))] if mk.numel() else torch.zeros_like(cc)
     catleft = okc & ((words >> (cc & 31)) & 1).bool()

@@ -1,8 +1,8 @@
 // K21 per-row outputs of a forest's root-to-leaf paths: exact path-dependent TreeSHAP feature contributions
 // (Lundberg et al. 2018, Algorithm 2, evaluated per leaf path instead of by recursion) and the leaf a row reaches
 // in every tree.  Split decisions are the predictors' (trees.hip): raw numeric left iff x <= thr as fp32 (NaN goes
-// right), raw categorical left iff the mask bit of (int)x is set (out of [0, 256) goes right); binned numeric left
-// iff bin <= node bin, binned set splits the mask bit of the bin.
+// right), raw categorical left iff the mask bit of (int)x is set (out of [0, 256) and NaN go right); binned numeric
+// left iff bin <= node bin, binned set splits the mask bit of the bin.
 #include "common.h"
 
 namespace {
@@ -35,8 +35,9 @@ __device__ __forceinline__ void stage_x_tile(float* __restrict__ sx, const float
 __device__ __forceinline__ bool raw_left(const float* __restrict__ xr, int fcode, int payload,
                                          const uint32_t* __restrict__ masks) {
   if (fcode >= 0) return xr[fcode] <= __int_as_float(payload);
-  const int c = (int)xr[-fcode - 2];
-  return (c >= 0 && c < 256) ? ((masks[payload * 8 + (c >> 5)] >> (c & 31)) & 1u) : false;
+  const float xc = xr[-fcode - 2];
+  const int c = (int)xc;  // xc > -1 && xc < 256  <=>  c in [0, 256), and false for NaN ((int)NaN is 0)
+  return (xc > -1.f && xc < 256.f) ? ((masks[payload * 8 + (c >> 5)] >> (c & 31)) & 1u) : false;
 }
 
 // How a row's feature value is fetched and tested.  A step is {feature code, payload, path goes left, slot}:

@@ -535,14 +535,29 @@ __global__ __launch_bounds__(256) void partition_kernel(const uint64_t* __restri
 // ---------------------------------------------------------------------------
 // K8 tree_predict on raw features.  Packed node = int4:
 //   continuous : {f, float_bits(thr), left, right}      left iff x <= thr
-//   categorical: {-(f+2), mask_off, left, right}        left iff bit (int)x
+//   categorical: {-(f+2), mask_off, left, right}        left iff bit (int)x; (int)x outside [0, 256) and NaN: right
 //   leaf       : {-1, value_off, 0, 0}                  values[value_off .. +K]
 // out[r][k] = base[k] + sum_t tree_w[t] * leafval_t(r)[k], all in fp64 (Spark's Double predictions): the leaf
 // values, tree weights and sums are doubles, and the sum has ONE fixed order that the host reference
 // (kernels.tree_predict on cpu) repeats bit for bit: tree lane q = t % 4 adds its trees in ascending order
 // (product rounded, then added: no FMA contraction), then base + lane 0 + lane 1 + lane 2 + lane 3.
-// Block = 256 threads = 64 rows x 4 tree lanes; the 64-row tile of X is staged in LDS with coalesced loads.
+// Block = 256 threads = 64 rows x 4 tree lanes; the 64-row tile of X is staged in LDS with coalesced loads, in the
+// way the host chose (stage_mode: it sees X's address, the kernels only follow).
 // ---------------------------------------------------------------------------
+// X tile staging of predict_kernel and predict_heap_kernel.  The float4 modes need rows without gaps, d % 4 == 0
+// and a 16-byte aligned X; the prefetch mode also a tile of at most kPredictPre float4s per thread (d <= 128).
+enum { kStageScalar = 0, kStageVec4 = 1, kStageVec4Pre = 2 };
+constexpr int kPredictPre = 8;
+
+inline int stage_mode(const float* X, int d, int64_t ldx, bool has_vec4_loop) {
+  if (ldx != d || (d % 4) != 0 || (reinterpret_cast<uintptr_t>(X) % 16) != 0) return kStageScalar;
+  if (64 * d / 4 <= kPredictPre * 256) return kStageVec4Pre;
+  return has_vec4_loop ? kStageVec4 : kStageScalar;
+}
+
+// STAGE is a template argument here: the kernel sits at the SGPR limit, and as one more kernel argument the mode
+// cost 2 more SGPR spills (7 for 5) and 1 % at 20 trees x 5e7 x 100; the prefetch instantiation spills none.
+template <int STAGE>
 __global__ __launch_bounds__(256) void predict_kernel(const float* __restrict__ X, int64_t n, int d, int64_t ldx,
                                                       const int4* __restrict__ nodes, const int* __restrict__ roots,
                                                       const double* __restrict__ tree_w, int T,
@@ -578,13 +593,13 @@ __global__ __launch_bounds__(256) void predict_kernel(const float* __restrict__ 
     tree_w = stw;
   }
   const int tl = threadIdx.x >> 6, row = threadIdx.x & 63;
-  const bool vec = ldx == d && (d % 4) == 0;
+  constexpr bool vec = STAGE != kStageScalar;
   // register double buffer: the next tile's float4s are in flight while this
   // tile's trees are walked (the single-buffered loop read X at ~1.8 TB/s)
-  constexpr int kPre = 8;
+  constexpr int kPre = kPredictPre;
   float4 pre[kPre];
   const int64_t stride = (int64_t)gridDim.x * 64;
-  const bool use_pre = vec && 64 * d / 4 <= kPre * 256;
+  constexpr bool use_pre = STAGE == kStageVec4Pre;
   auto fetch = [&](int64_t r0) {
     if (r0 >= n) return;
     const int rows = (int)((n - r0) < 64 ? (n - r0) : 64);
@@ -660,8 +675,9 @@ __global__ __launch_bounds__(256) void predict_kernel(const float* __restrict__ 
             if (nv[u].x >= 0) {
               left = xr[nv[u].x] <= __int_as_float(nv[u].y);
             } else {
-              const int c = (int)xr[-nv[u].x - 2];
-              left = (c >= 0 && c < 256) ? ((masks[nv[u].y * 8 + (c >> 5)] >> (c & 31)) & 1u) : false;
+              const float xc = xr[-nv[u].x - 2];
+              const int c = (int)xc;  // xc > -1 && xc < 256  <=>  c in [0, 256), and false for NaN ((int)NaN is 0)
+              left = (xc > -1.f && xc < 256.f) ? ((masks[nv[u].y * 8 + (c >> 5)] >> (c & 31)) & 1u) : false;
             }
             nv[u] = nd_src[left ? nv[u].z : nv[u].w];
             any = true;
@@ -707,7 +723,8 @@ __global__ __launch_bounds__(256) void predict_heap_kernel(const float* __restri
                                                            const int* __restrict__ heap, int depth,
                                                            const double* __restrict__ tree_w, int T,
                                                            const uint32_t* __restrict__ masks, double base,
-                                                           float* __restrict__ out, double* __restrict__ out_d) {
+                                                           float* __restrict__ out, double* __restrict__ out_d,
+                                                           int stage) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int NI = (1 << depth) - 1;     // internal slots per tree
@@ -720,11 +737,10 @@ __global__ __launch_bounds__(256) void predict_heap_kernel(const float* __restri
   for (int i = threadIdx.x; i < T * Wt; i += 256) sheap[i] = heap[i];
   for (int i = threadIdx.x; i < T; i += 256) stw[i] = tree_w[i];
   const int tl = threadIdx.x >> 6, row = threadIdx.x & 63;
-  const bool vec = ldx == d && (d % 4) == 0;
-  constexpr int kPre = 8;
+  constexpr int kPre = kPredictPre;
   float4 pre[kPre];
   const int64_t stride = (int64_t)gridDim.x * 64;
-  const bool use_pre = vec && 64 * d / 4 <= kPre * 256;
+  const bool use_pre = stage == kStageVec4Pre;  // this kernel has no float4 loop without the prefetch
   auto fetch = [&](int64_t r0) {
     if (r0 >= n) return;
     const int rows = (int)((n - r0) < 64 ? (n - r0) : 64);
@@ -781,8 +797,9 @@ __global__ __launch_bounds__(256) void predict_heap_kernel(const float* __restri
             if (nd.x >= 0) {
               idx[u] = 2 * idx[u] + (xr[nd.x] <= __int_as_float(nd.y) ? 1 : 2);
             } else if (nd.x < -1) {
-              const int c = (int)xr[-nd.x - 2];
-              const bool left = (c >= 0 && c < 256) ? ((masks[nd.y * 8 + (c >> 5)] >> (c & 31)) & 1u) : false;
+              const float xc = xr[-nd.x - 2];
+              const int c = (int)xc;  // as predict_kernel: a NaN category goes right
+              const bool left = (xc > -1.f && xc < 256.f) ? ((masks[nd.y * 8 + (c >> 5)] >> (c & 31)) & 1u) : false;
               idx[u] = 2 * idx[u] + (left ? 1 : 2);
             } else {
               idx[u] = 2 * idx[u] + 1;  // pass-through slot of a shallower leaf
@@ -860,6 +877,7 @@ __global__ __launch_bounds__(256) void heap_to_bins_kernel(const int* __restrict
 // not summed), so the five-step chains of its trees interleave.  heap: heap_to_bins_kernel's.
 // (PMC of the per-tree-guarded first version: 72 % of wave cycles waiting, 195 SALU + 90 LDS instructions per
 // wave and 64-row tile, LDS 24 % bank-conflict cycles: 5.04 ms at 1e8 x 100.)
+constexpr int kBinnedPre = 4;  // G <= 16 (d <= 128): 64 G words per tile = at most 4 per thread
 template <int NT>
 __global__ __launch_bounds__(256) void predict_heap_binned_kernel(const uint64_t* __restrict__ bins, int64_t n, int G,
                                                                   int d, const int* __restrict__ heap, int depth,
@@ -877,7 +895,7 @@ __global__ __launch_bounds__(256) void predict_heap_binned_kernel(const uint64_t
   for (int i = threadIdx.x; i < T * Wt; i += 256) sheap[i] = heap[i];
   for (int i = threadIdx.x; i < T; i += 256) stw[i] = tree_w[i];
   const int tl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), row = threadIdx.x & 63;
-  constexpr int kPre = 4;  // G <= 16 (d <= 128): 64 G words per tile = at most 4 per thread
+  constexpr int kPre = kBinnedPre;
   uint64_t pre[kPre];
   const int nw = 64 * G;
   const bool use_pre = nw <= kPre * 256;
@@ -993,6 +1011,66 @@ inline unsigned grid_for(int64_t n, int per, unsigned cap) {
   return (unsigned)g;
 }
 
+// The launch of predict_kernel, decided on the host from the call's shape and X's address alone (cdna_tree_predict
+// launches it, cdna_tree_predict_plan reports it).
+struct NodePredictPlan {
+  int stage, n_nodes, n_vals;
+  unsigned grid;
+  size_t lds;
+};
+
+int node_predict_plan(const float* X, int64_t n, int d, int64_t ldx, int64_t n_nodes_total, int T, int K,
+                      int64_t n_values, NodePredictPlan& p) {
+  const size_t lds0 = (size_t)64 * (d + 1) * 4 + (size_t)4 * 64 * K * 8;
+  if (lds0 > 160 * 1024) return (int)hipErrorInvalidValue;
+  // forest copy in LDS when it fits next to the tile (<= 64 KB per block keeps 2 blocks / CU)
+  p.n_nodes = p.n_vals = 0;
+  const size_t room = lds0 < 64 * 1024 ? 64 * 1024 - lds0 : 0;
+  p.n_nodes = n_nodes_total <= (int64_t)(room / 16) ? (int)n_nodes_total : 0;
+  const size_t vbytes = (size_t)(((n_values + 1) & ~1) + ((T + 1) & ~1)) * 8 + (size_t)((T + 3) & ~3) * 4;
+  if (p.n_nodes > 0 && n_values > 0 && (size_t)p.n_nodes * 16 + vbytes <= room) p.n_vals = (int)n_values;
+  p.lds = lds0 + (size_t)p.n_nodes * 16 + (p.n_vals > 0 ? vbytes : 0);
+  p.grid = grid_for(n, 64, 8192);
+  p.stage = stage_mode(X, d, ldx, true);
+  return 0;
+}
+
+// The launches of predict_heap_kernel (G == 0) and predict_heap_binned_kernel (G >= 1: the bins' word groups).
+// fits == false: over the 64 KB LDS budget, nothing is launched.  NT / passes / stage as the kernels' comments.
+struct HeapPredictPlan {
+  bool fits;
+  size_t lds;
+  int stage;       // fp32 rows: kStage*; bins: 1 when the next tile's words are prefetched into registers
+  unsigned grid;   // grid_mode 0
+  int nt, passes;  // bins only: trees per wave and pass, passes over a wave's trees
+};
+
+int heap_predict_plan(const float* X, int64_t n, int d, int64_t ldx, int depth, int T, int G, HeapPredictPlan& p) {
+  if (depth < 0 || depth > 12) return (int)hipErrorInvalidValue;
+  const size_t wt = ((size_t)4 << depth) - 2;
+  const size_t tile = G > 0 ? (size_t)64 * G * 8 : (size_t)64 * (d + 1) * 4;
+  p.lds = (size_t)T * wt * 4 + (size_t)((T + 1) & ~1) * 8 + tile + 256 * 8;
+  p.fits = p.lds <= 64 * 1024;
+  p.grid = grid_for(n, 64, 8192);
+  p.nt = p.passes = 0;
+  if (G > 0) {
+    // NT = trees per wave and pass: ceil(T / 4) up to 8 (one pass), else passes of 8
+    const int per_wave = (T + 3) / 4;
+    p.nt = per_wave < 1 ? 1 : (per_wave < 8 ? per_wave : 8);
+    p.passes = (per_wave + p.nt - 1) / p.nt;
+    p.stage = 64 * G <= kBinnedPre * 256 ? 1 : 0;
+  } else {
+    p.stage = stage_mode(X, d, ldx, false);
+  }
+  return 0;
+}
+
+// grid_mode 1 of cdna_tree_predict_heap: exactly the resident blocks, where that is fewer
+unsigned heap_resident_grid(const HeapPredictPlan& p) {
+  const unsigned res = cdna::resident_blocks(reinterpret_cast<const void*>(predict_heap_kernel), 256, p.lds);
+  return res > 0 && res < p.grid ? res : p.grid;
+}
+
 }  // namespace
 
 // miss_on: values that are NaN or equal miss_val are binned as -inf (XGBoost missing-value bin 0).
@@ -1106,18 +1184,35 @@ CDNA_API int cdna_tree_predict(const float* X, int64_t n, int d, int64_t ldx, co
                                const uint32_t* masks, int K, const double* base, double* out, int64_t n_values,
                                hipStream_t st) {
   if (n <= 0) return 0;
-  const size_t lds0 = (size_t)64 * (d + 1) * 4 + (size_t)4 * 64 * K * 8;
-  if (lds0 > 160 * 1024) return (int)hipErrorInvalidValue;
-  // forest copy in LDS when it fits next to the tile (<= 64 KB per block keeps 2 blocks / CU)
-  int n_nodes = 0, n_vals = 0;
-  const size_t room = lds0 < 64 * 1024 ? 64 * 1024 - lds0 : 0;
-  n_nodes = n_nodes_total <= (int64_t)(room / 16) ? (int)n_nodes_total : 0;
-  const size_t vbytes = (size_t)(((n_values + 1) & ~1) + ((T + 1) & ~1)) * 8 + (size_t)((T + 3) & ~3) * 4;
-  if (n_nodes > 0 && n_values > 0 && (size_t)n_nodes * 16 + vbytes <= room) n_vals = (int)n_values;
-  const size_t lds = lds0 + (size_t)n_nodes * 16 + (n_vals > 0 ? vbytes : 0);
-  hipLaunchKernelGGL(predict_kernel, dim3(grid_for(n, 64, 8192)), dim3(256), lds, st, X, n, d, ldx, nodes, roots,
-                     tree_w, T, values, masks, K, base, out, n_nodes, n_vals);
+  NodePredictPlan p;
+  const int bad = node_predict_plan(X, n, d, ldx, n_nodes_total, T, K, n_values, p);
+  if (bad != 0) return bad;
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, st, X, n, d, ldx, nodes, roots, tree_w, T, values, masks,
+                       K, base, out, p.n_nodes, p.n_vals);
+  };
+  switch (p.stage) {
+    case kStageVec4Pre: launch(predict_kernel<kStageVec4Pre>); break;
+    case kStageVec4: launch(predict_kernel<kStageVec4>); break;
+    default: launch(predict_kernel<kStageScalar>); break;
+  }
   return (int)hipGetLastError();
+}
+
+// What cdna_tree_predict would launch for this call (nothing is launched; X is only looked at as an address):
+// out[5] = {staging mode (0 scalar, 1 float4, 2 float4 + register prefetch), nodes in LDS, leaf values in LDS,
+// blocks, LDS bytes}.
+CDNA_API int cdna_tree_predict_plan(const float* X, int64_t n, int d, int64_t ldx, int64_t n_nodes_total, int T, int K,
+                                    int64_t n_values, int* out) {
+  NodePredictPlan p;
+  const int bad = node_predict_plan(X, n, d, ldx, n_nodes_total, T, K, n_values, p);
+  if (bad != 0) return bad;
+  out[0] = p.stage;
+  out[1] = p.n_nodes;
+  out[2] = p.n_vals;
+  out[3] = (int)p.grid;
+  out[4] = (int)p.lds;
+  return 0;
 }
 
 CDNA_API int cdna_predict_binned_add(const uint64_t* bins, int64_t n, const int4* nodes, int root,
@@ -1137,18 +1232,34 @@ CDNA_API int cdna_tree_predict_heap(const float* X, int64_t n, int d, int64_t ld
                                     const double* tree_w, int T, const uint32_t* masks, double base, float* out,
                                     double* out_d, int grid_mode, hipStream_t st) {
   if (n <= 0) return 0;
-  if (depth < 0 || depth > 12) return (int)hipErrorInvalidValue;
-  const size_t wt = ((size_t)4 << depth) - 2;
-  const size_t lds = (size_t)T * wt * 4 + (size_t)((T + 1) & ~1) * 8 + (size_t)64 * (d + 1) * 4 + 256 * 8;
-  if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
-  unsigned grid = grid_for(n, 64, 8192);
-  if (grid_mode & 1) {
-    const unsigned res = cdna::resident_blocks(reinterpret_cast<const void*>(predict_heap_kernel), 256, lds);
-    if (res > 0 && res < grid) grid = res;
-  }
-  hipLaunchKernelGGL(predict_heap_kernel, dim3(grid), dim3(256), lds, st, X, n, d, ldx, heap,
-                     depth, tree_w, T, masks, base, out, out_d);
+  HeapPredictPlan p;
+  const int bad = heap_predict_plan(X, n, d, ldx, depth, T, 0, p);
+  if (bad != 0) return bad;
+  if (!p.fits) return (int)hipErrorInvalidValue;
+  const unsigned grid = (grid_mode & 1) ? heap_resident_grid(p) : p.grid;
+  hipLaunchKernelGGL(predict_heap_kernel, dim3(grid), dim3(256), p.lds, st, X, n, d, ldx, heap,
+                     depth, tree_w, T, masks, base, out, out_d, p.stage);
   return (int)hipGetLastError();
+}
+
+// What cdna_tree_predict_heap (G == 0; X only as an address) or cdna_tree_predict_heap_binned (G >= 1; X unused)
+// would launch, without launching: out[8] = {fits the LDS budget, LDS bytes, staging mode (fp32 rows: 0 scalar,
+// 2 float4 + prefetch; bins: 1 = the next tile's words prefetched), blocks with grid_mode 0, blocks with grid_mode 1
+// (fp32 rows that fit; else 0), NT, passes (bins; else 0), 0}.
+CDNA_API int cdna_tree_predict_heap_plan(const float* X, int64_t n, int d, int64_t ldx, int depth, int T, int G,
+                                         int* out) {
+  HeapPredictPlan p;
+  const int bad = heap_predict_plan(X, n, d, ldx, depth, T, G, p);
+  if (bad != 0) return bad;
+  out[0] = p.fits ? 1 : 0;
+  out[1] = (int)p.lds;
+  out[2] = p.stage;
+  out[3] = (int)p.grid;
+  out[4] = (G == 0 && p.fits) ? (int)heap_resident_grid(p) : 0;
+  out[5] = p.nt;
+  out[6] = p.passes;
+  out[7] = 0;
+  return 0;
 }
 
 // predict_heap_binned_kernel: bins [G][n] u64 (binize's column groups), thr_up [d][Bup] fp32; the heap as
@@ -1159,15 +1270,16 @@ CDNA_API int cdna_tree_predict_heap_binned(const uint64_t* bins, int64_t n, int 
                                            double base, int* heap_b, float* out, double* out_d, hipStream_t st) {
   if (n <= 0) return 0;
   if (depth < 0 || depth > 12 || G < 1 || d < 1 || d > 8 * G || Bup < 1 || Bup > 256) return (int)hipErrorInvalidValue;
-  const size_t wt = ((size_t)4 << depth) - 2;
-  const size_t lds = (size_t)T * wt * 4 + (size_t)((T + 1) & ~1) * 8 + (size_t)64 * G * 8 + 256 * 8;
-  if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
-  const int64_t words = (int64_t)T * (int64_t)wt;
+  HeapPredictPlan p;
+  const int bad = heap_predict_plan(nullptr, n, d, 0, depth, T, G, p);
+  if (bad != 0) return bad;
+  if (!p.fits) return (int)hipErrorInvalidValue;
+  const size_t lds = p.lds;
+  const int64_t words = (int64_t)T * (int64_t)(((size_t)4 << depth) - 2);
   hipLaunchKernelGGL(heap_to_bins_kernel, dim3(grid_for(words, 256, 64)), dim3(256), 0, st, heap, T, depth, thr_up,
                      Bup, d, heap_b);
-  const dim3 grid(grid_for(n, 64, 8192));
-  // NT = trees per wave and pass: ceil(T / 4) up to 8 (one pass), else passes of 8
-  switch ((T + 3) / 4) {
+  const dim3 grid(p.grid);
+  switch (p.nt) {
     case 1: hipLaunchKernelGGL(predict_heap_binned_kernel<1>, grid, dim3(256), lds, st, bins, n, G, d, heap_b, depth,
                                tree_w, T, base, out, out_d); break;
     case 2: hipLaunchKernelGGL(predict_heap_binned_kernel<2>, grid, dim3(256), lds, st, bins, n, G, d, heap_b, depth,

@@ -96,16 +96,43 @@ def _thresholds(X, maxb):
     return thr, nthr
 
 
+# categorical values at the edges of bin = clamp(int(x), 0, 255), and their bins
+CAT_EDGES = [float("nan"), float("inf"), float("-inf"), 1e20, 3e9, -3.0, -0.5, 255.9, 256.0, 300.0]
+CAT_EDGE_BINS = [0, 255, 0, 255, 255, 0, 0, 255, 255, 255]
+
+
 def test_binize(dev):
+    """d = 21 is no multiple of 4: the LDS-tile kernel (binize v2)."""
     g = torch.Generator().manual_seed(1)
     X = torch.randn(3000, 21, generator=g)
     X[:, 3] = torch.randint(0, 9, (3000,), generator=g).float()
     thr, nthr = _thresholds(X, 40)
     nthr[3] = -1
     X[5, 2] = float("nan")
+    X[100:110, 3] = torch.tensor(CAT_EDGES)
     ref = K.binize(X, thr, nthr)
     out = K.binize(X.to(dev), thr.to(dev), nthr.to(dev)).cpu()
     assert torch.equal(out, ref)
+    assert out[0, 100:110, 3].tolist() == CAT_EDGE_BINS
+
+
+def test_binize_first_kernel_categorical_edges(dev):
+    """d = 151 with 255 thresholds: no multiple of 4 and a threshold table beyond the LDS-tile kernel's 150 KB, so the
+    first kernel (binize_kernel, thresholds read from global memory) runs -- it writes no row-major copy."""
+    g = torch.Generator().manual_seed(4)
+    n, d = 300, 151
+    X = torch.randn(n, d, generator=g)
+    X[:, 150] = torch.randint(0, 256, (n,), generator=g).float()
+    X[7, 2] = float("nan")
+    X[100:110, 150] = torch.tensor(CAT_EDGES)
+    thr = torch.randn(d, 255, generator=g).sort(1).values
+    nthr = torch.full((d,), 255, dtype=torch.int32)
+    nthr[150] = -1
+    ref = K.binize(X, thr, nthr)
+    out, rm = K.binize(X.to(dev), thr.to(dev), nthr.to(dev), want_rm=True)
+    assert rm is None
+    assert torch.equal(out.cpu(), ref)
+    assert out[150 // 8, 100:110, 150 % 8].tolist() == CAT_EDGE_BINS
 
 
 @pytest.mark.parametrize("lut", [256, 64, 0])
@@ -1233,9 +1260,11 @@ def test_binize_v5_matches_reference(dev, d, maxb, n, missing):
     X[9, 3 % d] = -float("inf")
     if missing is not None and not math.isnan(missing):
         X[11:40, 4 % d] = missing
+    X[50:60, 1] = torch.tensor(CAT_EDGES)
     ref = K.binize(X, thr, nthr, missing=missing)
     bins, rm = K.binize(X.to(dev), thr.to(dev), nthr.to(dev), missing=missing, want_rm=True)
     assert torch.equal(bins.cpu(), ref)
+    assert bins[0, 50:60, 1].tolist() == CAT_EDGE_BINS
     G = (d + 7) // 8
     rmc = rm.cpu()
     assert rm is not None and torch.equal(rmc[:, :G], K.bins_row_major(ref)) and not rmc[:, G:].any()

@@ -95,10 +95,12 @@ def hand_forests():
 
 @functools.lru_cache(maxsize=None)
 def hand_rows():
-    """200 rows: NaNs in numeric features, values exactly on thresholds, categories outside [0, 256)."""
+    """200 rows: NaNs in numeric features, values exactly on thresholds, categories outside [0, 256), and NaN
+    categories (every 9th row: _tree_b's mask has bit 0 set, so category 0 and NaN part there)."""
     rng = np.random.default_rng(7)
     X = rng.normal(size=(200, D)).astype(np.float32)
     X[:, CAT] = rng.choice([-3.0, 0.0, 1.0, 2.0, 2.7, 3.0, 200.0, 255.0, 256.0, 300.0, 1e10], size=200)
+    X[::9, CAT] = np.nan
     thr = np.array([0.5, -0.25, -0.5, 0.0, 1.0, 2.0, 0.75, -1.5], dtype=np.float32)
     for f in (0, 1, 2, 3, 5):
         hit = rng.uniform(size=200) < 0.25
@@ -111,7 +113,7 @@ def hand_rows():
 def _goes_left(forest, i, x):
     v = x[forest.feat[i]]
     if forest.is_cat[i]:
-        if not (v == v) or not 0 <= v < 256:  # NaN never reaches here (numeric features only hold NaNs)
+        if not (v == v) or not 0 <= v < 256:  # a NaN category goes right, like one outside [0, 256)
             return False
         c = int(v)
         return bool((int(forest.catmask[i][c >> 5]) >> (c & 31)) & 1)
