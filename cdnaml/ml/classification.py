@@ -1,4 +1,5 @@
 from ..models.classification import (DecisionTreeClassificationModel, DecisionTreeClassifier,  # noqa: F401
+                                     FMClassificationModel, FMClassifier,
                                      GBTClassificationModel, GBTClassifier, LinearSVC, LinearSVCModel,
                                      LogisticRegression, LogisticRegressionModel,
                                      MultilayerPerceptronClassificationModel, MultilayerPerceptronClassifier,

@@ -1,4 +1,5 @@
-from ..models.regression import (DecisionTreeRegressionModel, DecisionTreeRegressor, GBTRegressionModel,  # noqa: F401
+from ..models.regression import (DecisionTreeRegressionModel, DecisionTreeRegressor, FMRegressionModel,  # noqa: F401
+                                 FMRegressor, GBTRegressionModel,
                                  GBTRegressor, GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
                                  GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary,
                                  IsotonicRegression, IsotonicRegressionModel, LinearRegression,

@@ -7,7 +7,8 @@ sizes, fp32 device GEMMs above MULTINOMIAL_F64_MAX.  Tree
 classifiers (DT / RF / GBT) share the histogram engine with class-count
 statistics (gini / entropy).  MultilayerPerceptronClassifier: every L-BFGS evaluation is one pass of the fused
 K24 kernel (forward, softmax cross-entropy, backward and weight gradients on the fp32 MFMA) plus one all-reduce of
-P + 1 doubles.  Reference: MLE 03 - Logistic Regression
+P + 1 doubles.  FMClassifier: Spark's minibatch gradient descent, every iteration one pass of the fused K25 kernel
+(shared with FMRegressor in :mod:`.regression`).  Reference: MLE 03 - Logistic Regression
 Lab.py:99-158; Labs/ML 07L:42-209 (RandomForestClassifier + AUC).
 """
 from __future__ import annotations
@@ -26,8 +27,9 @@ from .base import Estimator, Model
 from .linalg import DenseMatrix, DenseVector
 from .optim import minimize
 from .param import NO_DEFAULT, TypeConverters as TC, keyword_init
-from .regression import (_GBT, _PRED, _RF, _TREE, _TreeModelBase, _bag_weights, _combine_weights, _default_seed,
-                         _num_classes, _subforest, resolve_subset, tree_fit_prepare)
+from .regression import (_FM_PARAMS, _GBT, _PRED, _RF, _TREE, _FMModel, _TreeModelBase, _bag_weights,
+                         _combine_weights, _default_seed, _fm_fit, _num_classes, _subforest, resolve_subset,
+                         tree_fit_prepare)
 from .tree.engine import ForestTrainer, TreeParams
 from .tree.forest import Forest
 from .util import VECTOR_F64_MAX, IllegalArgumentException, centered_gram, local_batch, local_xyw, require_vector
@@ -549,6 +551,72 @@ class MultilayerPerceptronClassificationModel(Model):
         self._layers = [int(v) for v in extra["layers"]]
         keyword_init(self, {"layers": self._layers})
         self.summary = None
+
+
+# ========================================================= FMClassifier
+_FMC_PARAMS = dict(_CLS, **{k: v for k, v in _FM_PARAMS.items() if k not in _PRED})
+
+
+class FMClassifier(Estimator):
+    """``pyspark.ml.classification.FMClassifier``: a binary factorization machine with the logistic loss, fitted by
+    Spark's minibatch gradient descent (``solver`` "gd" or "adamW"); see ``FMRegressor`` for the iteration, the row
+    selection and the initial factors.  Labels must be 0 or 1.  There is no ``weightCol`` (Spark has none), and the
+    training summary of Spark 3.1 (``FMClassificationTrainingSummary``) is not provided."""
+    _params = _FMC_PARAMS
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        keyword_init(self, kwargs)
+
+    def _fit(self, dataset):
+        lc = self.getLabelCol()
+
+        def binary(y, comm):
+            bad = torch.tensor([float(((y != 0) & (y != 1)).sum())], dtype=torch.float64, device=comm.device)
+            comm.all_reduce(bad)
+            if float(bad) > 0:
+                raise IllegalArgumentException(f"requirement failed: FMClassifier found {int(bad)} labels other "
+                                               f"than 0 and 1 in column {lc}: it is a binary classifier.")
+        theta, d, hist = _fm_fit(self, dataset, K.FM_LOGISTIC, binary)
+        model = FMClassificationModel(theta, d, self.getFactorSize(), self.getFitLinear(), self.getFitIntercept())
+        model._post_fit(self)
+        model.fitHistory = hist
+        return model
+
+
+class FMClassificationModel(_FMModel):
+    _params = _FMC_PARAMS
+    numClasses = 2
+
+    @staticmethod
+    def _outputs(r):
+        p = torch.sigmoid(r)
+        return torch.stack([-r, r], 1), torch.stack([1.0 - p, p], 1)
+
+    def predictRaw(self, features):
+        r = self._raw_one(features)
+        return DenseVector([-r, r])
+
+    def predictProbability(self, features):
+        return DenseVector(self._outputs(torch.tensor([self._raw_one(features)], dtype=torch.float64))[1][0].numpy())
+
+    def predict(self, features):
+        prob = self._outputs(torch.tensor([self._raw_one(features)], dtype=torch.float64))[1]
+        return float(_argmax_with_thresholds(prob, self.getThresholds())[0])
+
+    def _transform(self, dataset):
+        fc = self.getFeaturesCol()
+        require_vector(dataset, fc)
+        names = (self.getRawPredictionCol(), self.getPredictionCol(), self.getProbabilityCol())
+        thresholds = self.getThresholds()
+
+        def fn(b, ctx):
+            raw, prob = self._outputs(self._raw(b.columns[fc].values))
+            return _append_cls_outputs(b, raw, prob, _argmax_with_thresholds(prob, thresholds), names)
+        return dataset._new(MapPlan(dataset._plan, "FMClassificationModel", fn))
+
+    def __repr__(self):
+        return f"FMClassificationModel: uid={self.uid}, numFeatures={self.numFeatures}, factorSize={self._shape[0]}"
 
 
 # ========================================================= tree classifiers

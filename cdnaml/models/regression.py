@@ -8,6 +8,10 @@ further data passes are needed; cf. Labs/ML 02L:68-79 "matrix decomposition"
 first, iterative fallback).
 
 Tree regressors delegate to :mod:`cdnaml.models.tree.engine`.
+
+FMRegressor (and FMClassifier in :mod:`.classification`): Spark's minibatch gradient descent on the host, every
+iteration one pass of the fused K25 kernel (X [V | w], the fp64 top and the gradient on the fp32 MFMA) plus one
+all-reduce of P + 2 doubles.
 """
 from __future__ import annotations
 
@@ -24,14 +28,14 @@ from ..sql import types as T
 from ..sql.batch import ColumnData
 from ..sql.dataframe import MapPlan
 from .base import Estimator, Model
-from .linalg import DenseVector, SparseVector
+from .linalg import DenseMatrix, DenseVector, SparseVector
 from .param import NO_DEFAULT, TypeConverters as TC, keyword_init
 from .tree.binning import make_binned
 from .tree.engine import ForestTrainer, TreeParams
 from .tree import forest as _forest_mod
 from .tree.forest import FitBins, Forest
-from .util import (IllegalArgumentException, categorical_info, global_count, global_offset, gram_fp64_auto,
-                   local_batch, local_xyw, require_vector, streamed_columns)
+from .util import (IllegalArgumentException, categorical_info, feature_dtype, global_count, global_offset,
+                   gram_fp64_auto, local_batch, local_xyw, require_vector, streamed_columns)
 
 _PRED = {
     "featuresCol": ("features column name", "features", TC.toString),
@@ -1603,3 +1607,201 @@ class GeneralizedLinearRegressionModel(Model):
     def __repr__(self):
         return f"GeneralizedLinearRegressionModel: uid={self.uid}, family={self.getFamily()}, " \
                f"numFeatures={self.numFeatures}"
+
+
+# ============================================================ factorization machines
+_FM_PARAMS = dict(_PRED, **{
+    "factorSize": ("Dimensionality of the factor vectors, which are used to get pairwise interactions between "
+                   "variables", 8, TC.toInt),
+    "fitIntercept": ("whether to fit an intercept term", True, TC.toBoolean),
+    "fitLinear": ("whether to fit linear term (aka 1-way term)", True, TC.toBoolean),
+    "regParam": ("regularization parameter (>= 0)", 0.0, TC.toFloat),
+    "miniBatchFraction": ("fraction of the input data set that should be used for one iteration of gradient "
+                          "descent, in range (0, 1]", 1.0, TC.toFloat),
+    "initStd": ("standard deviation of initial coefficients", 0.01, TC.toFloat),
+    "maxIter": ("max number of iterations (>= 0)", 100, TC.toInt),
+    "stepSize": ("Step size to be used for each iteration of optimization (>= 0).", 1.0, TC.toFloat),
+    "tol": ("the convergence tolerance for iterative algorithms (>= 0)", 1e-6, TC.toFloat),
+    "solver": ("The solver algorithm for optimization. Supported options: gd, adamW.", "adamW", TC.toString),
+    "seed": ("random seed", None, TC.toInt),
+})
+
+
+def fm_initial_params(d: int, k: int, fit_linear: bool, fit_intercept: bool, init_std: float, seed: int) -> np.ndarray:
+    """V ~ N(0, initStd^2), w = 0, b = 0 in Spark's flat layout.  The normals are numpy's, drawn on the host from the
+    seed: the same on every device and number of ranks, but not the JVM's stream."""
+    theta = np.zeros(K.fm_num_params(d, k, fit_linear, fit_intercept))
+    theta[:d * k] = np.random.default_rng(int(seed) & 0xFFFFFFFFFFFFFFFF).normal(0.0, init_std, d * k)
+    return theta
+
+
+def fm_update_gd(theta, g, i: int, step_size: float, reg_param: float):
+    """Spark's SquaredL2Updater at iteration i (from 1): eta = stepSize / sqrt(i)."""
+    eta = step_size / math.sqrt(i)
+    return theta * (1.0 - eta * reg_param) - eta * g
+
+
+def fm_update_adamw(theta, g, state, i: int, step_size: float, reg_param: float):
+    """Spark's AdamWUpdater at iteration i (from 1); ``state`` holds the two moment vectors and is updated."""
+    b1, b2, eps = 0.9, 0.999, 1e-8
+    state["m"] = b1 * state["m"] + (1.0 - b1) * g
+    state["v"] = b2 * state["v"] + (1.0 - b2) * g * g
+    mh = state["m"] / (1.0 - b1 ** i)
+    vh = state["v"] / (1.0 - b2 ** i)
+    return theta - (step_size * mh / (np.sqrt(vh) + eps) + reg_param * theta)
+
+
+def fm_converged(prev, cur, tol: float) -> bool:
+    """GradientDescent.isConverged: |prev - cur|_2 < tol max(|cur|_2, 1)."""
+    return float(np.linalg.norm(prev - cur)) < tol * max(float(np.linalg.norm(cur)), 1.0)
+
+
+def _fm_fit(est, dataset, loss: int, check_labels=None):
+    """GradientDescent.runMiniBatchSGD on the host in fp64: every iteration is one ``K.fm_step`` over the local rows
+    plus one all-reduce of P + 2 doubles.  Returns (theta, d, per-iteration [mean loss, selected count])."""
+    solver, frac = est.getSolver(), est.getMiniBatchFraction()
+    if solver not in ("gd", "adamW"):
+        raise IllegalArgumentException(f"{type(est).__name__} solver must be gd or adamW, got {solver}")
+    if not 0.0 < frac <= 1.0:
+        raise IllegalArgumentException(f"{type(est).__name__} miniBatchFraction must be in (0, 1], got {frac}")
+    k = est.getFactorSize()
+    if k < 1:
+        raise IllegalArgumentException(f"{type(est).__name__} factorSize must be >= 1, got {k}")
+    lin, icpt = est.getFitLinear(), est.getFitIntercept()
+    X, y, _ = local_xyw(dataset, est.getFeaturesCol(), est.getLabelCol(), None, keep_f64=True)
+    session = dataset._session
+    comm = session.comm
+    n = X.shape[0]
+    dd = torch.tensor([float(X.shape[1]) if n else 0.0], dtype=torch.float64, device=comm.device)
+    comm.all_reduce(dd, "max")
+    d = int(dd)
+    if n == 0:
+        X = torch.zeros((0, d), dtype=X.dtype, device=X.device)
+    if check_labels is not None:
+        check_labels(y, comm)          # global: every rank raises, or none does
+    off = global_offset(session, n)
+    seed = est.getSeed() if est.getSeed() is not None else _default_seed(type(est))
+    theta = fm_initial_params(d, k, lin, icpt, est.getInitStd(), seed)
+    P = len(theta)
+    state = {"m": np.zeros(P), "v": np.zeros(P)}
+    step, reg, tol = est.getStepSize(), est.getRegParam(), est.getTol()
+    hist, updates = [], 0
+    for i in range(1, est.getMaxIter() + 1):
+        ls, g, cnt = K.fm_step(X, y, theta, k, loss, K.FM_STEP, lin, icpt,
+                               sample=(seed + i, off, frac) if frac < 1.0 else None)
+        acc = torch.cat([g, ls.reshape(1), cnt.reshape(1)])
+        comm.all_reduce(acc)
+        a = acc.cpu().numpy()
+        c = float(a[P + 1])
+        hist.append([a[P] / c if c > 0 else 0.0, c])
+        if c == 0:
+            continue
+        gm = a[:P] / c
+        new = fm_update_gd(theta, gm, i, step, reg) if solver == "gd" else \
+            fm_update_adamw(theta, gm, state, i, step, reg)
+        prev, theta = theta, new
+        updates += 1
+        if updates >= 2 and fm_converged(prev, theta, tol):
+            break
+    return theta, d, hist
+
+
+class _FMModel(Model):
+    """The parameters of a fitted factorization machine and its raw prediction."""
+
+    def __init__(self, theta=None, numFeatures=0, factorSize=None, fitLinear=True, fitIntercept=True):
+        super().__init__()
+        self._theta = np.asarray(theta if theta is not None else np.zeros(0), dtype=np.float64).reshape(-1)
+        self._d = int(numFeatures)
+        self._shape = (int(factorSize) if factorSize is not None else 0, bool(fitLinear), bool(fitIntercept))
+        self._prep = None
+        self.fitHistory = []      # per iteration [mean loss over the selected rows, selected rows]
+
+    @property
+    def numFeatures(self):
+        return self._d
+
+    def _parts(self):
+        k, lin, icpt = self._shape
+        return K.fm_unpack(torch.from_numpy(self._theta), self._d, k, lin, icpt)
+
+    @property
+    def intercept(self):
+        return float(self._parts()[2])
+
+    @property
+    def linear(self):
+        return DenseVector(self._parts()[1].numpy().copy())
+
+    @property
+    def factors(self):
+        return DenseMatrix(self._d, self._shape[0], self._parts()[0].numpy().reshape(-1).copy(), True)
+
+    def _prepared(self):
+        if self._prep is None:   # the device tables are built once per model, not per batch
+            self._prep = K.FmPrepared(self._theta, self._d, *self._shape)
+        return self._prep
+
+    def _raw(self, X: torch.Tensor) -> torch.Tensor:
+        k, lin, icpt = self._shape
+        if X.shape[0] == 0:
+            return torch.zeros(0, dtype=torch.float64, device=X.device)
+        X = X if feature_dtype(X) == torch.float64 else X.float()
+        return K.fm_step(X, None, self._theta, k, mode=K.FM_PREDICT, fit_linear=lin, fit_intercept=icpt,
+                         prepared=self._prepared())
+
+    def _raw_one(self, features) -> float:
+        x = np.asarray(features.toArray() if hasattr(features, "toArray") else features, dtype=np.float64)
+        return float(self._raw(torch.from_numpy(x.reshape(1, -1).copy()))[0])
+
+    def _save_state(self):
+        k, lin, icpt = self._shape
+        return {"numFeatures": self._d, "factorSize": k, "fitLinear": lin, "fitIntercept": icpt}, \
+            {"theta": torch.tensor(self._theta)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._theta = tensors["theta"].numpy()
+        self._d = int(extra["numFeatures"])
+        self._shape = (int(extra["factorSize"]), bool(extra["fitLinear"]), bool(extra["fitIntercept"]))
+        self._prep = None
+        self.fitHistory = []
+
+
+class FMRegressor(Estimator):
+    """``pyspark.ml.regression.FMRegressor``: a factorization machine with the squared loss, fitted by Spark's
+    minibatch gradient descent (``solver`` "gd" or "adamW").  Every iteration is one pass of the K25 ``fm_step`` op
+    over the local rows plus one all-reduce of P + 2 doubles; ``miniBatchFraction`` selects rows by a Philox draw
+    keyed by the global row id, so a fit does not depend on the number of ranks.  The initial factors follow Spark's
+    N(0, initStd^2) but come from numpy's generator, not the JVM's.  There is no ``weightCol`` (Spark has none), and
+    no training summary."""
+    _params = _FM_PARAMS
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        keyword_init(self, kwargs)
+
+    def _fit(self, dataset):
+        theta, d, hist = _fm_fit(self, dataset, K.FM_SQUARED)
+        model = FMRegressionModel(theta, d, self.getFactorSize(), self.getFitLinear(), self.getFitIntercept())
+        model._post_fit(self)
+        model.fitHistory = hist
+        return model
+
+
+class FMRegressionModel(_FMModel):
+    _params = _FM_PARAMS
+
+    def predict(self, features):
+        return self._raw_one(features)
+
+    def _transform(self, dataset):
+        fc, pc = self.getFeaturesCol(), self.getPredictionCol()
+        require_vector(dataset, fc)
+
+        def fn(b, ctx):
+            return b.with_column(pc, ColumnData(self._raw(b.columns[fc].values), T.DoubleType(),
+                                                b.columns[fc].valid))
+        return dataset._new(MapPlan(dataset._plan, f"FMRegressionModel -> {pc}", fn))
+
+    def __repr__(self):
+        return f"FMRegressionModel: uid={self.uid}, numFeatures={self.numFeatures}, factorSize={self._shape[0]}"

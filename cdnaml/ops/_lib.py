@@ -248,6 +248,11 @@ _SIGS = {
     "cdna_mlp_step_workspace": ([c_int64, c_void_p, c_int], c_int64),
     "cdna_mlp_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                        c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_fm_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p], c_int),
+    "cdna_fm_step_workspace": ([c_int64, c_int, c_int, c_int], c_int64),
+    "cdna_fm_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int,
+                      c_int, c_int, c_int, c_uint64, c_int64, c_double, c_uint32, c_void_p, c_void_p, c_void_p,
+                      c_void_p], c_int),
 }
 
 

@@ -2208,6 +2208,189 @@ def mlp_step(X: torch.Tensor, y: Optional[torch.Tensor], theta32, layers, mode: 
     return loss, torch.cat([t for W, b in zip(gW, gb) for t in (W.T.reshape(-1), b)])
 
 
+# ------------------------------------------------------------ K25 fm_step (fm.hip)
+FM_STEP, FM_PREDICT = 0, 1
+FM_SQUARED, FM_LOGISTIC = 0, 1
+FM_MAX_D = 128             # the fused kernel's range: d <= 128 and factorSize <= 32
+FM_MAX_K = 32
+FM_STREAM = 25             # Philox stream of the miniBatchFraction row selection
+FM_HOST_CHUNK = 1 << 18    # rows per pass of the host formulation
+
+
+def fm_num_params(d: int, k: int, fit_linear: bool = True, fit_intercept: bool = True) -> int:
+    return d * k + (d if fit_linear else 0) + (1 if fit_intercept else 0)
+
+
+def fm_unpack(theta, d: int, k: int, fit_linear: bool = True, fit_intercept: bool = True):
+    """(V [d, k], w [d], b) from Spark's flat vector: the factors row-major (entry (i, f) at i * k + f), then the d
+    linear weights if ``fit_linear``, then the intercept if ``fit_intercept`` (zeros for what is not fitted)."""
+    V = theta[:d * k].reshape(d, k)
+    w = theta[d * k:d * k + d] if fit_linear else theta.new_zeros(d)
+    b = theta[-1] if fit_intercept else theta.new_zeros(())
+    return V, w, b
+
+
+class FmPrepared:
+    """The parameters of one factorization machine as ``fm_step`` consumes them, prepared once per (device, row
+    dtype, path) and reused by every call that is given this object."""
+
+    def __init__(self, theta, d: int, k: int, fit_linear: bool = True, fit_intercept: bool = True):
+        self.shape = (int(d), int(k), bool(fit_linear), bool(fit_intercept))
+        self.theta = torch.as_tensor(theta, dtype=torch.float64).reshape(-1).cpu()
+        if self.theta.numel() != fm_num_params(*self.shape):
+            raise ValueError(f"fm_step: {self.theta.numel()} parameters for d = {d}, factorSize = {k}, fitLinear = "
+                             f"{fit_linear}, fitIntercept = {fit_intercept}, expected {fm_num_params(*self.shape)}")
+        self._made = {}
+
+    def on(self, dev, f32: bool, native: bool):
+        """(V, w, b) fp64 on ``dev`` (the parameters rounded to fp32 first for fp32 rows); for the native path the
+        kernel's operands instead: the zero-padded fp32 table [d up to 2][(k + 1) up to 32] whose row i is v_i, then
+        w_i with linear weights; u [128] fp64 with u_i = sum_f v_if^2; and the intercept."""
+        key = (str(dev), f32, native)
+        if key not in self._made:
+            d, k, lin, icpt = self.shape
+            th = self.theta.float().double() if f32 else self.theta
+            V, w, b = fm_unpack(th, d, k, lin, icpt)
+            if native:
+                plan = np.zeros(10, dtype=np.int64)
+                _lib.check(_lib.lib().cdna_fm_plan(None, 1, d, d, k, int(lin), plan.ctypes.data), "cdna_fm_plan")
+                ldw = int(plan[8])
+                tab = np.zeros((int(plan[7]) // ldw, ldw), dtype=np.float32)
+                tab[:d, :k] = V.numpy()
+                if lin:
+                    tab[:d, k] = w.numpy()
+                u = np.zeros(FM_MAX_D)
+                u[:d] = (V.numpy() ** 2).sum(1)
+                tab_d, u_d = upload(dev, tab.reshape(-1), u)
+                self._made[key] = (tab_d, u_d, float(b))
+            else:
+                self._made[key] = (V.to(dev).contiguous(), w.to(dev), b.to(dev))
+        return self._made[key]
+
+
+def _fm_native_plan(X: torch.Tensor, k: int, fit_linear: bool):
+    """cdna_fm_plan's answer for these operands (None: the host formulation) and X as the kernel takes it."""
+    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2:
+        return None, X
+    X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
+    out = np.zeros(10, dtype=np.int64)
+    _lib.check(_lib.lib().cdna_fm_plan(_ptr(X), X.shape[0], X.stride(0), X.shape[1], int(k), int(fit_linear),
+                                       out.ctypes.data), "cdna_fm_plan")
+    return (out if out[0] else None), X
+
+
+def fm_plan(X: torch.Tensor, k: int, fit_linear: bool = True) -> Dict[str, object]:
+    """What :func:`fm_step` runs for these operands, from the dispatch's own host function (nothing is launched):
+    ``path`` "native" or "host"; for the native path ``slots`` (gradient tiles per wave of the STEP instantiation: 1
+    or 2), ``vw`` (4: float4 row loads, 1: scalar loads), ``nblk``, ``rows_per_block``, ``tiles`` (32 x 32 gradient
+    tiles), ``lds`` (bytes per block) and ``fold_rows`` (rows a block accumulates in fp32 between folds into its
+    fp64 slab)."""
+    out, _ = _fm_native_plan(X, k, fit_linear)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "slots": int(out[1]), "vw": int(out[2]), "nblk": int(out[3]),
+            "rows_per_block": int(out[4]), "tiles": int(out[5]), "lds": int(out[6]), "fold_rows": int(out[9])}
+
+
+def fm_step(X: torch.Tensor, y: Optional[torch.Tensor], theta, k: int, loss: int = FM_SQUARED, mode: int = FM_STEP,
+            fit_linear: bool = True, fit_intercept: bool = True, sample=None, native: bool = True,
+            prepared: Optional[FmPrepared] = None):
+    """Loss and gradient sums, or the raw predictions, of a factorization machine over the local rows.
+
+    X [n, d] fp32 or fp64, y [n] (STEP only; 0 / 1 for the logistic loss), ``theta`` the flat parameter vector in
+    Spark's layout (see ``fm_unpack``), ``k`` the factor size.  Per row s_f = sum_i v_if x_i and
+    raw = b + w.x + 1/2 sum_f (s_f^2 - sum_i v_if^2 x_i^2).  FM_SQUARED: loss (raw - y)^2, m = 2 (raw - y).
+    FM_LOGISTIC: loss log1p(exp(-raw)) for y > 0 and log1p(exp(raw)) otherwise, m = sigmoid(raw) - y.  The gradient
+    is db = m, dw_i = m x_i, dv_if = m (s_f x_i - v_if x_i^2) (Spark's MSE / LogisticFactorizationMachinesGradient).
+
+    FM_STEP returns (loss_sum fp64 scalar, grad_sum fp64 [P], count fp64 scalar): un-normalised sums over the
+    selected rows and their number.  ``sample = (seed, row_offset, frac)`` selects row r when
+    ``uniform(seed, row_offset + r, FM_STREAM) < frac`` (the Philox of :func:`uniform`, keyed by the global row id,
+    so the selection does not depend on how the rows are sharded); ``frac >= 1`` or ``sample=None`` selects every row
+    without a draw.  FM_PREDICT returns raw [n] fp64.
+
+    For fp32 X the op is defined at the parameters rounded to fp32, on the device and in the host formulation alike;
+    fp64 X uses them as they are.  fp32 X on a GPU with d <= FM_MAX_D and k <= FM_MAX_K (any n >= 1, row stride and
+    alignment) runs the K25 kernel: X [V | w] and the gradient X^T (m s | m) on the exact-fp32 MFMA, the rest of raw,
+    the loss term and m in fp64, the selection drawn in the kernel, per-block partial sums reduced in a fixed order
+    (two calls on the same input return the same bits).  Everything else takes the host formulation: plain fp64
+    torch ops, FM_HOST_CHUNK rows at a time, the mask from :func:`uniform` (``native=False`` asks for it inside the
+    range too: bench/fm_micro.py times the two side by side).  ``prepared``: a FmPrepared of the same parameters, so
+    that repeated calls build the device tables once.
+    """
+    if X.dim() != 2:
+        raise ValueError("fm_step: X must be [n, d]")
+    n, d = X.shape
+    k = int(k)
+    dev = X.device
+    if loss not in (FM_SQUARED, FM_LOGISTIC) or mode not in (FM_STEP, FM_PREDICT):
+        raise ValueError(f"fm_step: loss {loss} / mode {mode}")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    f32 = X.dtype == torch.float32
+    shape = (int(d), k, bool(fit_linear), bool(fit_intercept))
+    prep = prepared if prepared is not None else FmPrepared(theta, *shape)
+    if prep.shape != shape:
+        raise ValueError(f"fm_step: prepared for {prep.shape}, called with {shape}")
+    P = prep.theta.numel()
+    seed, row_offset, frac = sample if sample is not None else (0, 0, 1.0)
+    draw = mode == FM_STEP and float(frac) < 1.0
+    plan, Xn = _fm_native_plan(X, k, fit_linear) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        tab, u, b0 = prep.on(dev, True, True)
+        out = ws = raw = yd = None
+        if mode == FM_STEP:
+            yd = y.to(device=dev, dtype=torch.float64).contiguous()
+            # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+            out = torch.empty(P + 2, dtype=torch.float64, device=dev)
+            ws = torch.empty(L.cdna_fm_step_workspace(n, d, k, int(fit_linear)), dtype=torch.float64, device=dev)
+        else:
+            raw = torch.empty(n, dtype=torch.float64, device=dev)
+        _lib.check(L.cdna_fm_step(_ptr(Xn), n, Xn.stride(0), _ptr(yd), _ptr(tab), _ptr(u), b0, d, k, int(fit_linear),
+                                  int(fit_intercept), int(loss), int(mode), int(draw),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), float(frac), FM_STREAM, _ptr(out),
+                                  _ptr(ws), _ptr(raw), _stream(dev)), "cdna_fm_step")
+        return (out[P], out[:P], out[P + 1]) if mode == FM_STEP else raw
+    # host formulation, FM_HOST_CHUNK rows at a time
+    V, w, b = prep.on(dev, f32, False)
+    V2 = V * V
+    lsum = torch.zeros((), dtype=torch.float64, device=dev)
+    cnt = torch.zeros((), dtype=torch.float64, device=dev)
+    gV, gw, gb = torch.zeros_like(V), torch.zeros_like(w), torch.zeros_like(b)
+    raws = []
+    yl = None if y is None else y.to(device=dev, dtype=torch.float64)
+    for i0 in range(0, n, FM_HOST_CHUNK):
+        Xc = X[i0:i0 + FM_HOST_CHUNK].double()
+        X2 = Xc * Xc
+        S = Xc @ V
+        r = b + Xc @ w + 0.5 * ((S * S).sum(1) - (X2 @ V2).sum(1))
+        if mode == FM_PREDICT:
+            raws.append(r)
+            continue
+        yc = yl[i0:i0 + FM_HOST_CHUNK]
+        if loss == FM_SQUARED:
+            l, m = (r - yc) ** 2, 2.0 * (r - yc)
+        else:
+            z = torch.where(yc > 0, -r, r)
+            l = z.clamp_min(0.0) + torch.log1p(torch.exp(-z.abs()))
+            m = torch.sigmoid(r) - yc
+        if draw:
+            sel = uniform(Xc.shape[0], seed, int(row_offset) + i0, FM_STREAM, device=dev) < float(frac)
+            l, m = torch.where(sel, l, torch.zeros_like(l)), torch.where(sel, m, torch.zeros_like(m))
+            cnt += sel.sum()
+        else:
+            cnt += Xc.shape[0]
+        lsum += l.sum()
+        gb += m.sum()
+        gw += Xc.T @ m
+        gV += Xc.T @ (S * m[:, None]) - V * (X2.T @ m)[:, None]
+    if mode == FM_PREDICT:
+        return torch.cat(raws) if raws else torch.zeros(0, dtype=torch.float64, device=dev)
+    parts = [gV.reshape(-1)] + ([gw] if fit_linear else []) + ([gb.reshape(1)] if fit_intercept else [])
+    return lsum, torch.cat(parts), cnt
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
