@@ -1,4 +1,5 @@
-from ..models.regression import (DecisionTreeRegressionModel, DecisionTreeRegressor, FMRegressionModel,  # noqa: F401
+from ..models.regression import (AFTSurvivalRegression, AFTSurvivalRegressionModel,  # noqa: F401
+                                 DecisionTreeRegressionModel, DecisionTreeRegressor, FMRegressionModel,
                                  FMRegressor, GBTRegressionModel,
                                  GBTRegressor, GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
                                  GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary,

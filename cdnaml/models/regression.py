@@ -12,6 +12,9 @@ Tree regressors delegate to :mod:`cdnaml.models.tree.engine`.
 FMRegressor (and FMClassifier in :mod:`.classification`): Spark's minibatch gradient descent on the host, every
 iteration one pass of the fused K25 kernel (X [V | w], the fp64 top and the gradient on the fp32 MFMA) plus one
 all-reduce of P + 2 doubles.
+
+AFTSurvivalRegression: L-BFGS on the host, every evaluation one pass of the fused fp64 K26 kernel plus one all-reduce
+of d + 4 doubles.
 """
 from __future__ import annotations
 
@@ -1805,3 +1808,155 @@ class FMRegressionModel(_FMModel):
 
     def __repr__(self):
         return f"FMRegressionModel: uid={self.uid}, numFeatures={self.numFeatures}, factorSize={self._shape[0]}"
+
+
+# ============================================================ AFT survival regression
+_AFT_PARAMS = dict(_PRED, **{
+    "censorCol": ("censor column name. The value of this column could be 0 or 1. If the value is 1, it means the "
+                  "event has occurred i.e. uncensored; otherwise censored.", "censor", TC.toString),
+    "quantileProbabilities": ("quantile probabilities array. Values of the quantile probabilities array should be "
+                              "in the range (0, 1) and the array should be non-empty.",
+                              [0.01, 0.05, 0.1, 0.25, 0.5, 0.75, 0.9, 0.95, 0.99], TC.toListFloat),
+    "quantilesCol": ("quantiles column name. This column will output quantiles of corresponding "
+                     "quantileProbabilities if it is set.", None, TC.toString),
+    "fitIntercept": ("whether to fit an intercept term", True, TC.toBoolean),
+    "maxIter": ("max number of iterations (>= 0)", 100, TC.toInt),
+    "tol": ("the convergence tolerance for iterative algorithms (>= 0)", 1e-6, TC.toFloat),
+    "aggregationDepth": ("suggested depth for treeAggregate (>= 2)", 2, TC.toInt),
+    "maxBlockSizeInMB": ("maximum memory in MB for stacking input data into blocks", 0.0, TC.toFloat),
+})
+
+
+def _aft_probs(stage):
+    """The stage's quantileProbabilities, checked: non-empty, every value in (0, 1)."""
+    probs = [float(p) for p in stage.getQuantileProbabilities()]
+    if not probs or not all(0.0 < p < 1.0 for p in probs):
+        raise IllegalArgumentException(f"{type(stage).__name__} quantileProbabilities must be a non-empty array of "
+                                       f"values in the range (0, 1), got {probs}")
+    return probs
+
+
+class AFTSurvivalRegression(Estimator):
+    """``pyspark.ml.regression.AFTSurvivalRegression``: the Weibull accelerated failure time model, fitted as Spark
+    fits it: no weights and no regularisation, the features scaled by their unbiased std (not centred) and the
+    coefficients scaled back, L-BFGS from the all-zero point (``optim.minimize``).  Every evaluation is one pass of
+    the K26 ``aft_step`` op over the local rows plus one all-reduce of d + 4 doubles.  The first evaluation also
+    validates the rows: there e^eps = t, so a row the op reports as bad has a label that is not positive and finite,
+    a censor other than 0 / 1 or a non-finite feature.  At a later point a bad row means e^eps overflowed: the
+    evaluation is +inf and the line search shortens the step.  ``aggregationDepth`` and ``maxBlockSizeInMB`` are
+    accepted and unused.  Spark has no training summary for this model, and there is none here."""
+    _params = _AFT_PARAMS
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        keyword_init(self, kwargs)
+        _aft_probs(self)
+
+    def _fit(self, dataset):
+        from .optim import minimize
+        from .util import centered_gram
+        _aft_probs(self)
+        X, y, cens = local_xyw(dataset, self.getFeaturesCol(), self.getLabelCol(), self.getCensorCol(),
+                               keep_f64=True)
+        session = dataset._session
+        comm = session.comm
+        n_loc = X.shape[0]
+        dd = torch.tensor([float(X.shape[1]) if n_loc else 0.0], dtype=torch.float64, device=comm.device)
+        comm.all_reduce(dd, "max")
+        d = int(dd)
+        if n_loc == 0:
+            X = torch.zeros((0, d), dtype=X.dtype, device=X.device)
+        n = global_count(session, n_loc)
+        if n == 0:
+            raise IllegalArgumentException("AFTSurvivalRegression: the training frame has no rows")
+        logt = torch.log(y)            # once per fit; t <= 0 or NaN gives a non-finite value: a bad row
+        _, _, Cg = centered_gram(X, comm)
+        sd = np.sqrt(np.clip(torch.diagonal(Cg).cpu().numpy(), 0, None) / max(n - 1, 1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = np.where(sd > 0, 1.0 / sd, 0.0)     # a zero-std feature takes no part, as in Spark
+        fit_int = self.getFitIntercept()
+        evals = [0]
+
+        def fg(theta):
+            b0 = theta[d] if fit_int else 0.0
+            ls, g, bad = K.aft_step(X, logt, cens, theta[:d] * inv, b0, theta[d + 1])
+            acc = torch.cat([g, ls.reshape(1), bad.reshape(1)])
+            comm.all_reduce(acc)
+            a = acc.cpu().numpy()
+            evals[0] += 1
+            if a[d + 3] > 0:
+                if evals[0] == 1:
+                    raise IllegalArgumentException(
+                        f"AFTSurvivalRegression: {int(a[d + 3])} rows are invalid: the label must be positive and "
+                        f"finite, the censor 0 or 1 and every feature finite")
+                return float("inf"), np.zeros(d + 2)
+            grad = a[:d + 2] / n
+            grad[:d] *= inv
+            if not fit_int:
+                grad[d] = 0.0
+            return a[d + 2] / n, grad
+
+        theta, _, _ = minimize(fg, np.zeros(d + 2), self.getMaxIter(), self.getTol())
+        model = AFTSurvivalRegressionModel(theta[:d] * inv, theta[d] if fit_int else 0.0, theta[d + 1])
+        model._post_fit(self)
+        return model
+
+
+class AFTSurvivalRegressionModel(Model):
+    _params = _AFT_PARAMS
+
+    def __init__(self, coefficients=None, intercept=0.0, logScale=0.0):
+        super().__init__()
+        self._coef = np.asarray(coefficients if coefficients is not None else [], dtype=np.float64).reshape(-1)
+        self._intercept = float(intercept)
+        self._log_scale = float(logScale)
+
+    @property
+    def coefficients(self):
+        return DenseVector(self._coef)
+
+    @property
+    def intercept(self):
+        return self._intercept
+
+    @property
+    def scale(self):
+        return math.exp(self._log_scale)
+
+    @property
+    def numFeatures(self):
+        return len(self._coef)
+
+    def predict(self, features):
+        x = np.asarray(features.toArray() if hasattr(features, "toArray") else features, dtype=np.float64)
+        return float(np.exp(x @ self._coef + self._intercept))
+
+    def predictQuantiles(self, features):
+        return DenseVector(self.predict(features) * K.aft_quantile_factors(_aft_probs(self), self._log_scale))
+
+    def _transform(self, dataset):
+        fc, pc, qc = self.getFeaturesCol(), self.getPredictionCol(), self.getQuantilesCol() or None
+        require_vector(dataset, fc)
+        probs = _aft_probs(self) if qc else None
+
+        def fn(b, ctx):
+            X = b.columns[fc].values
+            X = X if feature_dtype(X) == torch.float64 else X.float()
+            res = K.aft_step(X, None, None, self._coef, self._intercept, self._log_scale, K.AFT_PREDICT, probs)
+            valid = b.columns[fc].valid
+            if not qc:
+                return b.with_column(pc, ColumnData(res, T.DoubleType(), valid))
+            out = b.with_column(pc, ColumnData(res[0], T.DoubleType(), valid))
+            return out.with_column(qc, ColumnData(res[1], T.VectorUDT(), valid))
+        return dataset._new(MapPlan(dataset._plan, f"AFTSurvivalRegressionModel -> {pc}", fn))
+
+    def _save_state(self):
+        return {"intercept": self._intercept, "logScale": self._log_scale}, {"coefficients": torch.tensor(self._coef)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._coef = tensors["coefficients"].numpy()
+        self._intercept = float(extra["intercept"])
+        self._log_scale = float(extra["logScale"])
+
+    def __repr__(self):
+        return f"AFTSurvivalRegressionModel: uid={self.uid}, numFeatures={self.numFeatures}"

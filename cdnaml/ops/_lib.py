@@ -253,6 +253,10 @@ _SIGS = {
     "cdna_fm_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_uint64, c_int64, c_double, c_uint32, c_void_p, c_void_p, c_void_p,
                       c_void_p], c_int),
+    "cdna_aft_plan": ([c_void_p, c_int64, c_int64, c_int, c_void_p], c_int),
+    "cdna_aft_step_workspace": ([c_int64, c_int], c_int64),
+    "cdna_aft_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_int,
+                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

@@ -2391,6 +2391,142 @@ def fm_step(X: torch.Tensor, y: Optional[torch.Tensor], theta, k: int, loss: int
     return lsum, torch.cat(parts), cnt
 
 
+# ------------------------------------------------------------ K26 aft_step (aft.hip)
+AFT_STEP, AFT_PREDICT = 0, 1
+AFT_MAX_D = 128            # the fused kernel's range: fp32 rows with d <= 128
+AFT_MAX_Q = 16             # quantiles written by the PREDICT pass itself; more take one outer product on top
+AFT_HOST_CHUNK = 1 << 18   # rows per pass of the host formulation
+
+
+def aft_quantile_factors(probs, log_sigma: float) -> np.ndarray:
+    """exp(sigma log(-log(1 - p))) per quantile probability: the Weibull quantile over the prediction."""
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    return np.exp(math.exp(float(log_sigma)) * np.log(-np.log1p(-p)))
+
+
+def _aft_native_plan(X: torch.Tensor):
+    """cdna_aft_plan's answer for these operands (None: the host formulation) and X as the kernel takes it."""
+    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2:
+        return None, X
+    X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
+    out = np.zeros(6, dtype=np.int64)
+    _lib.check(_lib.lib().cdna_aft_plan(_ptr(X), X.shape[0], X.stride(0), X.shape[1], out.ctypes.data),
+               "cdna_aft_plan")
+    return (out if out[0] else None), X
+
+
+def aft_plan(X: torch.Tensor) -> Dict[str, object]:
+    """What :func:`aft_step` runs for these operands, from the dispatch's own host function (nothing is launched):
+    ``path`` "native" or "host"; for the native path ``vw`` (4: float4 row loads, 1: scalar loads), ``nblk``,
+    ``rows_per_block``, ``lds`` (bytes per block) and ``slot`` (workspace doubles per block)."""
+    out, _ = _aft_native_plan(X)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "vw": int(out[1]), "nblk": int(out[2]), "rows_per_block": int(out[3]),
+            "lds": int(out[4]), "slot": int(out[5])}
+
+
+def aft_step(X: torch.Tensor, logt: Optional[torch.Tensor], censor: Optional[torch.Tensor], coef, intercept: float,
+             log_sigma: float, mode: int = AFT_STEP, probs=None, native: bool = True):
+    """Loss and gradient sums, or the predictions and quantiles, of Spark's AFTSurvivalRegression (a Weibull
+    accelerated failure time model) over the local rows.
+
+    X [n, d] fp32 or fp64, ``logt`` [n] the log of the survival times, ``censor`` [n] (1: the event occurred, 0:
+    censored), ``coef`` [d] fp64 for the rows as they are, sigma = exp(``log_sigma``).  Per row
+    eps = (log t - x.coef - intercept) / sigma, the loss term is delta log sigma - delta eps + e^eps,
+    m = (delta - e^eps) / sigma, and the gradient terms are m x (coef), m (intercept) and
+    delta + (delta - e^eps) eps (log sigma).
+
+    AFT_STEP returns (loss_sum fp64 scalar, grad_sums fp64 [d + 2] = [coef | intercept | log sigma], bad fp64
+    scalar): un-normalised sums, and the number of bad rows.  A row is bad when it has a non-finite feature or
+    log t (t <= 0 or NaN), a censor that is neither 0 nor 1, or a loss, m or log-sigma term that is not finite
+    (e^eps overflowed); a bad row adds exactly nothing to the other sums.  AFT_PREDICT returns exp(x.coef +
+    intercept) [n] fp64, and with ``probs`` also the quantiles [n, Q] = prediction * exp(sigma log(-log(1 - p))).
+
+    fp32 X on a GPU with d <= AFT_MAX_D (any n >= 1, row stride and alignment) runs the K26 kernel: one pass, all
+    arithmetic in fp64, per-block partial sums reduced in a fixed order (two calls on the same input return the same
+    bits); up to AFT_MAX_Q quantiles are written by the same pass.  Everything else takes the host formulation: plain
+    fp64 torch ops, AFT_HOST_CHUNK rows at a time (``native=False`` asks for it inside the range too:
+    bench/aft_micro.py times the two side by side).
+    """
+    if X.dim() != 2:
+        raise ValueError("aft_step: X must be [n, d]")
+    if mode not in (AFT_STEP, AFT_PREDICT):
+        raise ValueError(f"aft_step: mode {mode}")
+    n, d = X.shape
+    dev = X.device
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    cf = np.asarray(coef.detach().cpu().numpy() if isinstance(coef, torch.Tensor) else coef,
+                    dtype=np.float64).reshape(-1)
+    if cf.shape[0] != d:
+        raise ValueError(f"aft_step: {cf.shape[0]} coefficients for d = {d}")
+    b0, ls = float(intercept), float(log_sigma)
+    sigma = math.exp(ls)
+    qf = None if probs is None or mode != AFT_PREDICT else aft_quantile_factors(probs, ls)
+    Q = 0 if qf is None else int(qf.shape[0])
+    if mode == AFT_STEP:
+        logt = logt.to(device=dev, dtype=torch.float64).contiguous()
+        censor = censor.to(device=dev, dtype=torch.float64).contiguous()
+        if logt.shape != (n,) or censor.shape != (n,):
+            raise ValueError("aft_step: logt and censor must be [n]")
+    plan, Xn = _aft_native_plan(X) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        inner = qf is not None and 0 < Q <= AFT_MAX_Q
+        if inner:
+            cf_d, qf_d = upload(dev, cf, qf)
+        else:
+            cf_d, qf_d = upload(dev, cf)[0], None
+        out = ws = pred = quant = None
+        if mode == AFT_STEP:
+            # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+            out = torch.empty(d + 4, dtype=torch.float64, device=dev)
+            ws = torch.empty(L.cdna_aft_step_workspace(n, d), dtype=torch.float64, device=dev)
+        else:
+            pred = torch.empty(n, dtype=torch.float64, device=dev)
+            quant = torch.empty((n, Q), dtype=torch.float64, device=dev) if inner else None
+        _lib.check(L.cdna_aft_step(_ptr(Xn), n, Xn.stride(0), _ptr(logt), _ptr(censor), _ptr(cf_d), b0, sigma, ls, d,
+                                   int(mode), Q if inner else 0, _ptr(qf_d), _ptr(out), _ptr(ws), _ptr(pred),
+                                   _ptr(quant), _stream(dev)), "cdna_aft_step")
+        if mode == AFT_STEP:
+            return out[d + 2], out[:d + 2], out[d + 3]
+        if qf is None:
+            return pred
+        return pred, (quant if inner else torch.outer(pred, upload(dev, qf)[0]))
+    # host formulation, AFT_HOST_CHUNK rows at a time
+    cf_t = torch.from_numpy(cf).to(dev)
+    acc = torch.zeros(d + 4, dtype=torch.float64, device=dev)
+    preds = []
+    for i0 in range(0, n, AFT_HOST_CHUNK):
+        Xc = X[i0:i0 + AFT_HOST_CHUNK].double()
+        dot = Xc @ cf_t
+        if mode == AFT_PREDICT:
+            preds.append(torch.exp(dot + b0))
+            continue
+        lt, dl = logt[i0:i0 + AFT_HOST_CHUNK], censor[i0:i0 + AFT_HOST_CHUNK]
+        eps = (lt - dot - b0) / sigma
+        ee = torch.exp(eps)
+        loss = dl * ls - dl * eps + ee
+        mm = (dl - ee) / sigma
+        ss = dl + (dl - ee) * eps
+        ok = torch.isfinite(Xc).all(1) & torch.isfinite(lt) & ((dl == 0) | (dl == 1)) & torch.isfinite(loss) & \
+            torch.isfinite(mm) & torch.isfinite(ss)
+        zero = torch.zeros_like(loss)
+        mm = torch.where(ok, mm, zero)
+        acc[:d] += torch.where(ok[:, None], Xc, zero[:, None]).T @ mm      # predicated: never a NaN times zero
+        acc[d] += mm.sum()
+        acc[d + 1] += torch.where(ok, ss, zero).sum()
+        acc[d + 2] += torch.where(ok, loss, zero).sum()
+        acc[d + 3] += (~ok).sum()
+    if mode == AFT_STEP:
+        return acc[d + 2], acc[:d + 2], acc[d + 3]
+    pred = torch.cat(preds) if preds else torch.zeros(0, dtype=torch.float64, device=dev)
+    if qf is None:
+        return pred
+    return pred, torch.outer(pred, torch.from_numpy(qf).to(dev))
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
