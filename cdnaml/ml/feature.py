@@ -3,3 +3,6 @@ from ..models.feature import (Bucketizer, Imputer, ImputerModel, IndexToString, 
                               MinMaxScalerModel, Normalizer, OneHotEncoder, OneHotEncoderModel, PCA, PCAModel,
                               QuantileDiscretizer, RFormula, RFormulaModel, SQLTransformer, StandardScaler,
                               StandardScalerModel, StringIndexer, StringIndexerModel, VectorAssembler)
+from ..models.feature import (ChiSqSelector, ChiSqSelectorModel, UnivariateFeatureSelector,  # noqa: F401
+                              UnivariateFeatureSelectorModel, VarianceThresholdSelector,
+                              VarianceThresholdSelectorModel)

@@ -1,4 +1,5 @@
-"""``pyspark.ml.stat``: Correlation and Summarizer over device feature matrices."""
+"""``pyspark.ml.stat``: Correlation, Summarizer and the univariate hypothesis tests (ChiSquareTest, ANOVATest,
+FValueTest) over device feature matrices."""
 import numpy as np
 import pandas as pd
 import torch
@@ -178,3 +179,227 @@ def summarize_groups(c, wcol, gid: torch.Tensor, G: int, param):
                             else T.VectorUDT(), True) for m in metrics]
     structs = [Row(**{m: r[m] for m in metrics}) for r in rows]
     return ColumnData(torch.zeros(G, device=dev), T.StructType(fields), meta={"_py": structs})
+
+
+# ============================================================ univariate tests (K27 label_stats)
+MAX_CATEGORIES = 10000         # Spark's limit on the distinct values of a chi-square feature or label
+COUNT_MAX_CELLS = 1 << 24      # a wider contingency table [d][K][C] is formed per feature from the distinct values
+
+
+def _label_codes(y: torch.Tensor, comm):
+    """(distinct label values over all ranks, ascending; this rank's rows as int32 ranks among them)."""
+    from ..models.feature import SparkException
+    loc = torch.unique(y).cpu().numpy() if y.numel() else np.zeros(0)
+    vals = np.unique(np.concatenate([np.asarray(v, dtype=np.float64) for v in comm.all_gather_object(loc)]))
+    if len(vals) > MAX_CATEGORIES:
+        raise SparkException(f"Chi-square test expect factors (categorical values) but found more than "
+                             f"{MAX_CATEGORIES} distinct label values.")
+    codes = torch.searchsorted(torch.from_numpy(vals).to(y.device), y).to(torch.int32) if y.numel() else \
+        torch.zeros(0, dtype=torch.int32, device=y.device)
+    return vals, codes
+
+
+def _shift(V: torch.Tensor, comm) -> torch.Tensor:
+    """The shift of ``util.centered_gram`` for the columns of V (a vector of labels: one column), fp64; every rank
+    gets the same one.  A mean that is not finite (the F tests report such values afterwards) becomes 0."""
+    from ..models.util import lead_mean
+    sh = lead_mean(V[:, None] if V.dim() == 1 else V, comm)
+    return torch.where(torch.isfinite(sh), sh, torch.zeros_like(sh))
+
+
+def _reduced(parts, comm) -> np.ndarray:
+    """One all-reduce of the statistics' parts as fp64 (counts are exact below 2^53); the host copy, flat."""
+    flat = torch.cat([p.reshape(-1).double() for p in parts])
+    comm.all_reduce(flat)
+    return flat.cpu().numpy()
+
+
+def _chi2_of_table(O: np.ndarray):
+    """(statistic, p-value, degrees of freedom) of a contingency table; categories and labels that do not occur
+    are dropped (Spark's factors are the distinct values that occur)."""
+    from scipy.stats import chi2
+    O = np.asarray(O, dtype=np.float64)
+    O = O[O.sum(1) > 0][:, O.sum(0) > 0]
+    if O.shape[0] > MAX_CATEGORIES:
+        from ..models.feature import SparkException
+        raise SparkException(f"Chi-square test expect factors (categorical values) but found more than "
+                             f"{MAX_CATEGORIES} distinct values.")
+    df = (O.shape[0] - 1) * (O.shape[1] - 1) if O.size else 0
+    if df <= 0:
+        return 0.0, 1.0, 0
+    E = np.outer(O.sum(1), O.sum(0)) / O.sum()
+    stat = float(((O - E) ** 2 / E).sum())
+    return stat, float(chi2.sf(stat, df)), int(df)
+
+
+def _distinct_table(x: torch.Tensor, codes: torch.Tensor, C: int, comm) -> np.ndarray:
+    """The contingency table of one feature from its distinct values (any doubles: the categories are their
+    ranks), over all ranks."""
+    from ..models.feature import SparkException
+    xv = x.double().cpu().numpy()
+    uv, inv = np.unique(xv, return_inverse=True)
+    tab = np.zeros((len(uv), C), dtype=np.int64)
+    np.add.at(tab, (inv.reshape(-1), codes.cpu().numpy().astype(np.int64)), 1)
+    got = comm.all_gather_object((uv, tab))
+    vals = np.unique(np.concatenate([g[0] for g in got]))
+    if len(vals) > MAX_CATEGORIES:
+        raise SparkException(f"Chi-square test expect factors (categorical values) but found more than "
+                             f"{MAX_CATEGORIES} distinct values.")
+    out = np.zeros((len(vals), C), dtype=np.int64)
+    for u, t in got:
+        if len(u):
+            np.add.at(out, np.searchsorted(vals, u), t)
+    return out
+
+
+def chi_square_scores(dataset, featuresCol, labelCol):
+    """(pValues, degreesOfFreedom, statistics) per feature, numpy: Pearson's chi-square test of independence of
+    every feature against the label, both taken as categorical."""
+    from ..models.util import categorical_info, local_xyw
+    comm = dataset._session.comm
+    X, y, _ = local_xyw(dataset, featuresCol, labelCol, keep_f64=True)
+    n, d = X.shape
+    vals, codes = _label_codes(y, comm)
+    C = len(vals)
+    if C == 0 or d == 0:
+        return np.ones(d), np.zeros(d, dtype=np.int64), np.zeros(d)
+    arity = categorical_info(dataset.schema[featuresCol].metadata, d, featuresCol)
+    if len(arity) == d:
+        Kc = max(arity.values())
+    else:
+        mx = float(torch.where(torch.isfinite(X), X, torch.zeros_like(X)).amax()) if n else 0.0
+        Kc = int(min(max(comm.all_reduce_scalar(mx, "max"), 0.0), 2.0 ** 40)) + 1
+    if d * Kc * C <= COUNT_MAX_CELLS:
+        st = K.label_stats(X, codes, K.LABEL_COUNT, C=C, K=Kc)
+        flat = _reduced([st["table"], st["bad"]], comm)
+        table = np.rint(flat[:d * Kc * C]).astype(np.int64).reshape(d, Kc, C)
+        bad = flat[d * Kc * C:] > 0
+    else:
+        table, bad = None, np.ones(d, dtype=bool)
+    p, dof, stat = np.ones(d), np.zeros(d, dtype=np.int64), np.zeros(d)
+    for j in range(d):
+        # a feature with values that are not category indices below K: from its distinct values, as Spark does
+        O = _distinct_table(X[:, j], codes, C, comm) if bad[j] else table[j]
+        stat[j], p[j], dof[j] = _chi2_of_table(O)
+    return p, dof, stat
+
+
+def _require_clean(bad: np.ndarray, bad_label: float, what: str):
+    from ..models.util import IllegalArgumentException
+    if bad_label > 0:
+        raise IllegalArgumentException(f"{what}: the label has {int(bad_label)} values that are not finite")
+    if (bad > 0).any():
+        j = int(np.argmax(bad > 0))
+        raise IllegalArgumentException(f"{what}: feature {j} has {int(bad[j])} values that are not finite")
+
+
+def anova_scores(dataset, featuresCol, labelCol):
+    """(pValues, degreesOfFreedom, fValues) per feature, numpy: the one-way ANOVA F-test of every continuous
+    feature against a categorical label (Spark's computeANOVA; sklearn's f_classif)."""
+    from scipy.stats import f as f_dist
+    from ..models.util import local_xyw
+    comm = dataset._session.comm
+    X, y, _ = local_xyw(dataset, featuresCol, labelCol, keep_f64=True)
+    d = X.shape[1]
+    vals, codes = _label_codes(y, comm)
+    C = max(len(vals), 1)
+    st = K.label_stats(X, codes, K.LABEL_CLASS, C=C, shift=_shift(X, comm))
+    flat = _reduced([st["sums"], st["sq"], st["n"], st["bad"], st["bad_label"]], comm)
+    sums, sq = flat[:C * d].reshape(C, d), flat[C * d:C * d + d]
+    nc, bad, bad_label = flat[C * d + d:C * d + d + C], flat[C * d + d + C:C * d + 2 * d + C], flat[-1]
+    _require_clean(bad, bad_label, "ANOVATest")
+    keep = nc > 0
+    sums, nc = sums[keep], nc[keep]
+    n, Cn = nc.sum(), int(keep.sum())
+    S = sums.sum(0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        between = (sums ** 2 / nc[:, None]).sum(0) - S ** 2 / n
+        within = (sq - S ** 2 / n) - between
+        dfb, dfw = Cn - 1, n - Cn
+        F = (between / dfb) / (within / dfw)
+        p = f_dist.sf(F, dfb, dfw)
+    return p, np.full(d, int(n) - 1, dtype=np.int64), F
+
+
+def fvalue_scores(dataset, featuresCol, labelCol):
+    """(pValues, degreesOfFreedom, fValues) per feature, numpy: the F-test of the Pearson correlation of every
+    continuous feature with a continuous label (sklearn's f_regression)."""
+    from scipy.stats import f as f_dist
+    from ..models.util import local_xyw
+    comm = dataset._session.comm
+    X, y, _ = local_xyw(dataset, featuresCol, labelCol, keep_f64=True)
+    d = X.shape[1]
+    st = K.label_stats(X, y, K.LABEL_REGRESS, shift=_shift(X, comm), yshift=float(_shift(y, comm)[0]))
+    flat = _reduced([st["sx"], st["sxx"], st["sxy"], st["bad"], st["sy"], st["syy"], st["n"], st["bad_label"]], comm)
+    sx, sxx, sxy, bad = flat[:d], flat[d:2 * d], flat[2 * d:3 * d], flat[3 * d:4 * d]
+    sy, syy, n, bad_label = flat[4 * d:]
+    _require_clean(bad, bad_label, "FValueTest")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = (sxy - sx * sy / n) / np.sqrt((sxx - sx ** 2 / n) * (syy - sy ** 2 / n))
+        F = r ** 2 / (1.0 - r ** 2) * (n - 2)
+        p = f_dist.sf(F, 1, n - 2)
+    return p, np.full(d, int(n) - 2, dtype=np.int64), F
+
+
+def _test_frame(dataset, p, dof, stat, stat_name, flatten, long_dof):
+    """The tests' result as a DataFrame of the dataset's session: one row of vectors, or one row per feature."""
+    from ..sql import types as T
+    from ..sql.batch import Batch, ColumnData
+    sess = dataset._session
+    dev = sess.device
+    it = T.LongType() if long_dof else T.IntegerType()
+    tdt = torch.int64 if long_dof else torch.int32
+    d = len(p)
+    a, b = sess._rank_slice(d if flatten else 1)      # the rows are spread over the ranks like any local table
+    if flatten:
+        cols = {"featureIndex": ColumnData(torch.arange(a, b, dtype=torch.int32, device=dev), T.IntegerType()),
+                "pValue": ColumnData(torch.from_numpy(p[a:b].astype(np.float64)).to(dev), T.DoubleType()),
+                "degreesOfFreedom": ColumnData(torch.from_numpy(dof[a:b].astype(np.int64)).to(dev, tdt), it),
+                stat_name: ColumnData(torch.from_numpy(stat[a:b].astype(np.float64)).to(dev), T.DoubleType())}
+    else:
+        k = b - a
+
+        def vec(v):
+            return ColumnData(torch.from_numpy(np.asarray(v, np.float64))[None, :].to(dev)[:k], T.VectorUDT())
+        # the array of integers rides as host objects, like the group engine's struct rows
+        cols = {"pValues": vec(p),
+                "degreesOfFreedom": ColumnData(torch.zeros(k, device=dev), T.ArrayType(it),
+                                               meta={"_py": [[int(v) for v in dof]] * k}),
+                stat_name + "s": vec(stat)}                # statistics / fValues
+    batch = Batch(cols, b - a, dev)
+    return sess._from_local_batches("LocalTableScan", lambda: [batch], batch.schema())
+
+
+class ChiSquareTest:
+    """``pyspark.ml.stat.ChiSquareTest``: Pearson's independence test of every feature against the label.  The
+    label's categories are its distinct values; a feature's are its values as category indices (the contingency
+    tables of all features come from one pass of K27 ``label_stats``), and a feature with other values (not
+    integers, negative) is recounted from its distinct values, as Spark does.  More than 10000 distinct values
+    raise."""
+
+    @staticmethod
+    def test(dataset, featuresCol, labelCol, flatten=False):
+        p, dof, stat = chi_square_scores(dataset, featuresCol, labelCol)
+        return _test_frame(dataset, p, dof, stat, "statistic", flatten, long_dof=False)
+
+
+class ANOVATest:
+    """``pyspark.ml.stat.ANOVATest``: the one-way ANOVA F-test of every continuous feature against a categorical
+    label.  A feature value that is not finite raises IllegalArgumentException naming the first such feature
+    (Spark returns NaN there); AFTSurvivalRegression validates its rows the same way."""
+
+    @staticmethod
+    def test(dataset, featuresCol, labelCol, flatten=False):
+        p, dof, stat = anova_scores(dataset, featuresCol, labelCol)
+        return _test_frame(dataset, p, dof, stat, "fValue", flatten, long_dof=True)
+
+
+class FValueTest:
+    """``pyspark.ml.stat.FValueTest``: the F-test of every continuous feature's correlation with a continuous
+    label.  A feature value or label that is not finite raises IllegalArgumentException naming the first such
+    feature (Spark returns NaN there); AFTSurvivalRegression validates its rows the same way."""
+
+    @staticmethod
+    def test(dataset, featuresCol, labelCol, flatten=False):
+        p, dof, stat = fvalue_scores(dataset, featuresCol, labelCol)
+        return _test_frame(dataset, p, dof, stat, "fValue", flatten, long_dof=True)

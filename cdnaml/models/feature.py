@@ -908,3 +908,203 @@ class PCAModel(Model):
 
     def _load_state(self, extra, tensors, stages):
         self._pc, self._ev = tensors["pc"].numpy(), tensors["ev"].numpy()
+
+
+# ============================================================ feature selectors
+SELECTION_MODES = ("numTopFeatures", "percentile", "fpr", "fdr", "fwe")
+
+
+def select_by_pvalues(p_values, mode: str, threshold: float) -> List[int]:
+    """Spark's selection of feature indices from the tests' p-values, in ascending index order.
+    ``numTopFeatures``: the k smallest p-values (the sort is stable: ties go to the lower index); ``percentile``: the
+    top int(d p); ``fpr``: p < alpha; ``fdr``: Benjamini-Hochberg -- with the p-values sorted, the largest i with
+    p_(i) <= alpha (i + 1) / d selects the first i + 1; ``fwe``: p < alpha / d."""
+    p = np.asarray(p_values, dtype=np.float64)
+    d = len(p)
+    order = np.argsort(p, kind="stable")
+    if mode == "numTopFeatures":
+        sel = order[:max(int(threshold), 0)]
+    elif mode == "percentile":
+        sel = order[:int(d * float(threshold))]
+    elif mode == "fpr":
+        sel = np.nonzero(p < threshold)[0]
+    elif mode == "fdr":
+        ok = np.nonzero(p[order] <= float(threshold) * (np.arange(d) + 1) / max(d, 1))[0]
+        sel = order[:int(ok[-1]) + 1] if len(ok) else order[:0]
+    elif mode == "fwe":
+        sel = np.nonzero(p < float(threshold) / max(d, 1))[0]
+    else:
+        raise IllegalArgumentException(f"selection mode {mode!r} is not among {list(SELECTION_MODES)}")
+    return sorted(int(i) for i in sel)
+
+
+class _SelectorModel(Model):
+    """A vector slicer over ``selectedFeatures``: the output keeps the input's dtype and carries the selected slots'
+    ML attributes, re-indexed (a tree model behind the selector still sees the nominal arities)."""
+
+    def __init__(self, selectedFeatures=None):
+        super().__init__()
+        self._selected = [int(i) for i in (selectedFeatures if selectedFeatures is not None else [])]
+
+    @property
+    def selectedFeatures(self):
+        return list(self._selected)
+
+    def _transform(self, dataset):
+        ic, oc = self.getFeaturesCol(), self.getOutputCol()
+        require_vector(dataset, ic)
+        sel = list(self._selected)
+
+        def fn(b: Batch, ctx):
+            col = b.columns[ic]
+            X = col.values
+            if sel and X.shape[1] <= max(sel):
+                raise IllegalArgumentException(f"{type(self).__name__}: column {ic} has {X.shape[1]} slots, "
+                                               f"feature {max(sel)} was selected")
+            Y = X[:, torch.tensor(sel, dtype=torch.long, device=X.device)].contiguous()
+            attrs = vector_attrs(col.meta, X.shape[1], ic)
+            out = []
+            for i, j in enumerate(sel):
+                a = dict(attrs[j])
+                a["idx"] = i
+                out.append(a)
+            meta = {"ml_attr": {"attrs": out, "num_attrs": len(out)}}
+            return b.with_column(oc, ColumnData(Y, T.VectorUDT(), col.valid, meta=meta))
+        return dataset._new(MapPlan(dataset._plan, f"{type(self).__name__} -> {oc}", fn))
+
+    def _save_state(self):
+        return {"selectedFeatures": list(self._selected)}, {}
+
+    def _load_state(self, extra, tensors, stages):
+        self._selected = [int(i) for i in extra["selectedFeatures"]]
+
+
+_UFS_DEFAULT_THRESHOLD = {"numTopFeatures": 50, "percentile": 0.1, "fpr": 0.05, "fdr": 0.05, "fwe": 0.05}
+
+
+class UnivariateFeatureSelector(Estimator):
+    """``pyspark.ml.feature.UnivariateFeatureSelector``: features chosen by a univariate test against the label
+    -- chi-square (categorical features, categorical label), ANOVA F (continuous, categorical) or the F-value
+    (continuous, continuous); each is one pass of K27 ``label_stats`` and one all-reduce.  A feature value that is
+    not finite raises in the two F tests (see ``ml.stat``)."""
+    _params = {
+        "featuresCol": ("features column name", "features", TC.toString),
+        "outputCol": ("output column name", NO_DEFAULT, TC.toString),
+        "labelCol": ("label column name", "label", TC.toString),
+        "featureType": ("the feature type: 'categorical' or 'continuous'", NO_DEFAULT, TC.toString),
+        "labelType": ("the label type: 'categorical' or 'continuous'", NO_DEFAULT, TC.toString),
+        "selectionMode": ("the selection mode: " + ", ".join(SELECTION_MODES), "numTopFeatures", TC.toString),
+        "selectionThreshold": ("the upper bound of the features that the selector will select", NO_DEFAULT,
+                               TC.toFloat),
+    }
+
+    def __init__(self, featuresCol=None, outputCol=None, labelCol=None, selectionMode=None):
+        super().__init__()
+        keyword_init(self, dict(featuresCol=featuresCol, outputCol=outputCol, labelCol=labelCol,
+                                selectionMode=selectionMode))
+
+    def getSelectionThreshold(self):
+        """The set threshold, else the selection mode's default: 50 features, the top 0.1, or alpha = 0.05."""
+        if self.isSet("selectionThreshold"):
+            return self.getOrDefault("selectionThreshold")
+        mode = self.getSelectionMode()
+        if mode not in _UFS_DEFAULT_THRESHOLD:
+            raise IllegalArgumentException(f"selection mode {mode!r} is not among {list(SELECTION_MODES)}")
+        return _UFS_DEFAULT_THRESHOLD[mode]
+
+    def _score_function(self):
+        if not self.isSet("featureType") or not self.isSet("labelType"):
+            raise IllegalArgumentException("UnivariateFeatureSelector: featureType and labelType must be set")
+        ft, lt = self.getFeatureType(), self.getLabelType()
+        from ..ml import stat
+        fn = {("categorical", "categorical"): stat.chi_square_scores,
+              ("continuous", "categorical"): stat.anova_scores,
+              ("continuous", "continuous"): stat.fvalue_scores}.get((ft, lt))
+        if fn is None:
+            raise IllegalArgumentException(f"Unsupported combination: featureType={ft}, labelType={lt}")
+        return fn
+
+    def _fit(self, dataset):
+        fn = self._score_function()
+        thr = self.getSelectionThreshold()
+        p, _, _ = fn(dataset, self.getFeaturesCol(), self.getLabelCol())
+        return UnivariateFeatureSelectorModel(select_by_pvalues(p, self.getSelectionMode(), thr))
+
+
+class UnivariateFeatureSelectorModel(_SelectorModel):
+    _params = UnivariateFeatureSelector._params
+
+
+class ChiSqSelector(Estimator):
+    """``pyspark.ml.feature.ChiSqSelector``: the chi-square test's selection under Spark's older parameter names."""
+    _params = {
+        "featuresCol": ("features column name", "features", TC.toString),
+        "outputCol": ("output column name", NO_DEFAULT, TC.toString),
+        "labelCol": ("label column name", "label", TC.toString),
+        "numTopFeatures": ("number of features the selector will select", 50, TC.toInt),
+        "selectorType": ("the selector type: " + ", ".join(SELECTION_MODES), "numTopFeatures", TC.toString),
+        "percentile": ("percentile of features the selector will select", 0.1, TC.toFloat),
+        "fpr": ("the highest p-value for features to be kept", 0.05, TC.toFloat),
+        "fdr": ("the upper bound of the expected false discovery rate", 0.05, TC.toFloat),
+        "fwe": ("the upper bound of the expected family-wise error rate", 0.05, TC.toFloat),
+    }
+
+    def __init__(self, numTopFeatures=None, featuresCol=None, outputCol=None, labelCol=None, selectorType=None,
+                 percentile=None, fpr=None, fdr=None, fwe=None):
+        super().__init__()
+        keyword_init(self, dict(numTopFeatures=numTopFeatures, featuresCol=featuresCol, outputCol=outputCol,
+                                labelCol=labelCol, selectorType=selectorType, percentile=percentile, fpr=fpr, fdr=fdr,
+                                fwe=fwe))
+
+    def _fit(self, dataset):
+        from ..ml import stat
+        mode = self.getSelectorType()
+        if mode not in SELECTION_MODES:
+            raise IllegalArgumentException(f"selector type {mode!r} is not among {list(SELECTION_MODES)}")
+        thr = self.getOrDefault(mode)
+        p, _, _ = stat.chi_square_scores(dataset, self.getFeaturesCol(), self.getLabelCol())
+        return ChiSqSelectorModel(select_by_pvalues(p, mode, thr))
+
+
+class ChiSqSelectorModel(_SelectorModel):
+    _params = ChiSqSelector._params
+
+
+class VarianceThresholdSelector(Estimator):
+    """``pyspark.ml.feature.VarianceThresholdSelector``: the features whose unbiased variance is greater than
+    ``varianceThreshold``; the moments are K20's (``col_moments``), merged over the ranks."""
+    _params = {
+        "featuresCol": ("features column name", "features", TC.toString),
+        "outputCol": ("output column name", NO_DEFAULT, TC.toString),
+        "varianceThreshold": ("features with a variance not greater than this are removed", 0.0, TC.toFloat),
+    }
+
+    def __init__(self, featuresCol=None, outputCol=None, varianceThreshold=None):
+        super().__init__()
+        keyword_init(self, dict(featuresCol=featuresCol, outputCol=outputCol, varianceThreshold=varianceThreshold))
+
+    def _fit(self, dataset):
+        from ..ops import kernels as K
+        from .util import local_xyw
+        X, _, _ = local_xyw(dataset, self.getFeaturesCol(), keep_f64=True)
+        comm = dataset._session.comm
+        d = X.shape[1]
+        mom = K.col_moments(X)[:, :3].double() if X.shape[0] else torch.zeros((d, 3), dtype=torch.float64,
+                                                                             device=X.device)
+        # (count, mean, M2) of every rank, merged pairwise in rank order (Chan et al.)
+        parts = comm.all_gather_object(mom.cpu().numpy())
+        n, mean, m2 = np.zeros(d), np.zeros(d), np.zeros(d)
+        for q in parts:
+            nb, mb, sb = q[:, 0], q[:, 1], q[:, 2]
+            tot = n + nb
+            with np.errstate(divide="ignore", invalid="ignore"):
+                delta = mb - mean
+                m2 = np.where(nb > 0, m2 + sb + delta ** 2 * n * nb / np.where(tot > 0, tot, 1.0), m2)
+                mean = np.where(nb > 0, mean + delta * nb / np.where(tot > 0, tot, 1.0), mean)
+            n = tot
+        var = m2 / np.maximum(n - 1, 1)
+        return VarianceThresholdSelectorModel([int(i) for i in np.nonzero(var > self.getVarianceThreshold())[0]])
+
+
+class VarianceThresholdSelectorModel(_SelectorModel):
+    _params = VarianceThresholdSelector._params

@@ -184,6 +184,18 @@ def gram_fp64_auto(n: int, d: int) -> bool:
     return float(n) * (d + 2) ** 2 <= GRAM_FP64_MAX_WORK
 
 
+def lead_mean(X: torch.Tensor, comm, lead: int = 1024) -> torch.Tensor:
+    """A common estimate of the column means, fp64 [d]: the mean of every rank's leading rows, averaged over the
+    ranks that have any.  Every rank gets the same one: the shift of ``centered_gram`` and of the univariate tests."""
+    k = min(X.shape[0], lead)
+    sh = X[:k].double().mean(0) if k else torch.zeros(X.shape[1], dtype=torch.float64, device=X.device)
+    if comm.distributed:
+        cnt = torch.full((1,), 1.0 if k else 0.0, dtype=torch.float64, device=X.device)
+        comm.all_reduce_many([sh, cnt])
+        sh = sh / cnt.clamp_min(1.0)
+    return sh
+
+
 def centered_gram(X: torch.Tensor, comm, lead: int = 1024):
     """(n, mean[d], C[d, d]) over all ranks, C = sum (x - mean)(x - mean)^T, all fp64 (the Gram in fp64 arithmetic
     at course sizes: ``gram_fp64_auto``, so a feature standardisation equals the host's to rounding).
@@ -194,13 +206,7 @@ def centered_gram(X: torch.Tensor, comm, lead: int = 1024):
     """
     from ..ops import kernels as K
     n_loc, d = X.shape
-    k = min(n_loc, lead)
-    sh = X[:k].double().mean(0) if k else torch.zeros(d, dtype=torch.float64, device=X.device)
-    if comm.distributed:
-        cnt = torch.full((1,), 1.0 if k else 0.0, dtype=torch.float64, device=X.device)
-        comm.all_reduce_many([sh, cnt])
-        sh = sh / cnt.clamp_min(1.0)
-    sh = sh.float()
+    sh = lead_mean(X, comm, lead).float()
     G = K.gram(X, shift=sh, fp64=X.dtype == torch.float64 or gram_fp64_auto(n_loc, d)) if n_loc else \
         torch.zeros((d + 2, d + 2), dtype=torch.float64, device=X.device)
     comm.all_reduce(G)

@@ -257,6 +257,10 @@ _SIGS = {
     "cdna_aft_step_workspace": ([c_int64, c_int], c_int64),
     "cdna_aft_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_int,
                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_label_stats_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p], c_int),
+    "cdna_label_stats_workspace": ([c_int64, c_int, c_int, c_int, c_int], c_int64),
+    "cdna_label_stats": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int,
+                          c_int, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

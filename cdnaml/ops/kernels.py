@@ -2527,6 +2527,170 @@ def aft_step(X: torch.Tensor, logt: Optional[torch.Tensor], censor: Optional[tor
     return pred, torch.outer(pred, torch.from_numpy(qf).to(dev))
 
 
+# ------------------------------------------------------------ K27 label_stats (select.hip)
+LABEL_COUNT, LABEL_CLASS, LABEL_REGRESS = 0, 1, 2
+LABEL_MAX_D = 128              # the fused kernel's range: fp32 rows with d <= 128
+LABEL_MAX_C = 32               # CLASS: classes of the kernel's LDS table
+LABEL_HOST_CHUNK = 1 << 18     # rows per pass of the host formulation
+
+
+def _label_native_plan(X: torch.Tensor, mode: int, C: int, K: int):
+    """cdna_label_stats_plan's answer for these operands (None: the host formulation), X as the kernel takes it and
+    the plan's constants (the COUNT table's LDS budget)."""
+    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2:
+        return None, X
+    X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
+    out = np.zeros(8, dtype=np.int64)
+    C, K = min(int(C), 1 << 30), min(int(K), 1 << 30)
+    _lib.check(_lib.lib().cdna_label_stats_plan(_ptr(X), X.shape[0], X.stride(0), X.shape[1], int(mode), C, K,
+                                                out.ctypes.data), "cdna_label_stats_plan")
+    return (out if out[0] else None), X
+
+
+def label_stats_plan(X: torch.Tensor, mode: int, C: int = 1, K: int = 1) -> Dict[str, object]:
+    """What :func:`label_stats` runs for these operands, from the dispatch's own host function (nothing is
+    launched): ``path`` "native" or "host"; for the native path ``vw`` (4: float4 row loads, 1: scalar loads),
+    ``nblk``, ``rows_per_block``, ``lds`` (bytes per block), ``slot`` (workspace doubles per block),
+    ``count_budget`` (the LDS bytes a COUNT table may take) and ``blocks_per_cu`` (by LDS)."""
+    out, _ = _label_native_plan(X, mode, C, K)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "vw": int(out[1]), "nblk": int(out[2]), "rows_per_block": int(out[3]),
+            "lds": int(out[4]), "slot": int(out[5]), "count_budget": int(out[6]), "blocks_per_cu": int(out[7])}
+
+
+def label_stats(X: torch.Tensor, label: torch.Tensor, mode: int, C: int = 1, K: int = 1, shift=None,
+                yshift: float = 0.0, native: bool = True) -> Dict[str, torch.Tensor]:
+    """The per-feature statistics of X [n, d] against a label that the univariate tests need, over the local rows.
+
+    LABEL_COUNT (chi-square): ``label`` holds codes in 0 .. C-1; returns ``table`` int64 [d, K, C], the exact
+    counts of the cells (feature, int(x), code).  A cell is bad when x is non-finite, not integer-valued, < 0
+    or >= K.
+    LABEL_CLASS (ANOVA): codes in 0 .. C-1 and ``shift`` [d] fp64; returns ``sums`` [C, d] = sum (x - shift) per
+    (class, feature), ``sq`` [d] = sum (x - shift)^2 and ``n`` [C], the rows per class, all fp64 and formed from
+    (double)x - shift.  A cell is bad when x is non-finite.
+    LABEL_REGRESS (F-value): ``label`` is y fp64, with ``shift`` and ``yshift``; returns ``sx``, ``sxx``, ``sxy``
+    [d] = sum (x - shift), its square and (x - shift)(y - yshift), and ``sy``, ``syy``, ``n``: sum (y - yshift), its
+    square and the number of rows.  A cell is bad when x is non-finite.
+    Every mode returns ``bad`` [d], the bad cells per feature -- a bad cell adds nothing to its feature's
+    statistics -- and ``bad_label``: the rows whose label is bad (a code outside 0 .. C-1, a non-finite y), which are
+    never accumulated.  The counts are int64 in LABEL_COUNT and fp64 (exact) in the other modes.
+
+    fp32 X on a GPU with d <= LABEL_MAX_D (any n >= 1, row stride and alignment) runs the K27 kernel: one pass;
+    LABEL_CLASS with 2 <= C <= LABEL_MAX_C, LABEL_COUNT while the block's table of K C cells per feature fits the
+    kernel's LDS budget (:func:`label_stats_plan` reports it).  Sums are fp64 per-block partials reduced in a
+    fixed order and the counts go through integer atomics: two calls on the same input return the same bits.
+    Everything else takes the host formulation: plain fp64 torch ops, LABEL_HOST_CHUNK rows at a time
+    (``native=False`` asks for it inside the range too: bench/select_micro.py times the two side by side).
+    """
+    if X.dim() != 2:
+        raise ValueError("label_stats: X must be [n, d]")
+    if mode not in (LABEL_COUNT, LABEL_CLASS, LABEL_REGRESS):
+        raise ValueError(f"label_stats: mode {mode}")
+    n, d = X.shape
+    dev = X.device
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    C, K = (1, 1) if mode == LABEL_REGRESS else (int(C), int(K) if mode == LABEL_COUNT else 1)
+    if C < 1 or K < 1:
+        raise ValueError(f"label_stats: C = {C}, K = {K}")
+    if label.shape != (n,):
+        raise ValueError("label_stats: the label must be [n]")
+    if mode == LABEL_REGRESS:
+        label = label.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        label = label.to(device=dev, dtype=torch.int32).contiguous()
+    sh = None
+    if mode != LABEL_COUNT:
+        sh = np.zeros(d) if shift is None else np.asarray(
+            shift.detach().cpu().numpy() if isinstance(shift, torch.Tensor) else shift, dtype=np.float64).reshape(-1)
+        if sh.shape[0] != d:
+            raise ValueError(f"label_stats: {sh.shape[0]} shifts for d = {d}")
+    ys = float(yshift)
+    plan, Xn = _label_native_plan(X, mode, C, K) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        if mode == LABEL_COUNT:
+            # cleared by the call itself
+            out = torch.empty(d * K * C + d + 1, dtype=torch.int64, device=dev)
+            _lib.check(L.cdna_label_stats(_ptr(Xn), n, Xn.stride(0), _ptr(label), None, None, 0.0, d, int(mode), C, K,
+                                          _ptr(out), None, _stream(dev)), "cdna_label_stats")
+            return {"table": out[:d * K * C].view(d, K, C), "bad": out[d * K * C:d * K * C + d],
+                    "bad_label": out[d * K * C + d]}
+        sh_d = upload(dev, sh)[0]
+        slot = int(plan[5])
+        # every entry of out is written by the reduction, every workspace entry it reads by the pass
+        out = torch.empty(slot, dtype=torch.float64, device=dev)
+        ws = torch.empty(L.cdna_label_stats_workspace(n, d, int(mode), C, K), dtype=torch.float64, device=dev)
+        is_y = mode == LABEL_REGRESS
+        _lib.check(L.cdna_label_stats(_ptr(Xn), n, Xn.stride(0), None if is_y else _ptr(label),
+                                      _ptr(label) if is_y else None, _ptr(sh_d), ys, d, int(mode), C, K, _ptr(out),
+                                      _ptr(ws), _stream(dev)), "cdna_label_stats")
+        D = LABEL_MAX_D
+        if mode == LABEL_CLASS:
+            return {"sums": out[:C * D].view(C, D)[:, :d], "sq": out[C * D:C * D + d],
+                    "bad": out[C * D + D:C * D + D + d], "n": out[C * D + 2 * D:C * D + 2 * D + C],
+                    "bad_label": out[C * D + 2 * D + C]}
+        return {"sx": out[:d], "sxx": out[D:D + d], "sxy": out[2 * D:2 * D + d], "bad": out[3 * D:3 * D + d],
+                "sy": out[4 * D], "syy": out[4 * D + 1], "n": out[4 * D + 2], "bad_label": out[4 * D + 3]}
+    # host formulation, LABEL_HOST_CHUNK rows at a time
+    f64 = dict(dtype=torch.float64, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    if mode == LABEL_COUNT:
+        table = torch.zeros(d * K * C, **i64)
+        bad, bad_label = torch.zeros(d, **i64), torch.zeros((), **i64)
+        cols = torch.arange(d, device=dev)[None, :]
+        for i0 in range(0, n, LABEL_HOST_CHUNK):
+            Xc = X[i0:i0 + LABEL_HOST_CHUNK].double()
+            yl = label[i0:i0 + LABEL_HOST_CHUNK].long()
+            ok = (yl >= 0) & (yl < C)
+            good = torch.isfinite(Xc) & (Xc >= 0) & (Xc < K) & (Xc == torch.floor(Xc)) & ok[:, None]
+            k = torch.where(good, Xc, torch.zeros_like(Xc)).long()
+            idx = (cols * K + k) * C + torch.where(ok, yl, torch.zeros_like(yl))[:, None]
+            table += torch.bincount(idx[good], minlength=d * K * C)
+            bad += (~good & ok[:, None]).sum(0)
+            bad_label += (~ok).sum()
+        return {"table": table.view(d, K, C), "bad": bad, "bad_label": bad_label}
+    sh_t = torch.from_numpy(sh).to(dev)
+    bad, bad_label = torch.zeros(d, **f64), torch.zeros((), **f64)
+    if mode == LABEL_CLASS:
+        sums, sq, cnt = torch.zeros((C, d), **f64), torch.zeros(d, **f64), torch.zeros(C, **f64)
+        for i0 in range(0, n, LABEL_HOST_CHUNK):
+            Xc = X[i0:i0 + LABEL_HOST_CHUNK].double()
+            yl = label[i0:i0 + LABEL_HOST_CHUNK].long()
+            ok = (yl >= 0) & (yl < C)
+            yz = torch.where(ok, yl, torch.zeros_like(yl))
+            fin = torch.isfinite(Xc)
+            V = torch.where(fin & ok[:, None], Xc - sh_t, torch.zeros_like(Xc))   # predicated: never a NaN times zero
+            if C <= 64:    # a one-hot product: index_add_'s fp64 atomics on a few rows serialise on a GPU
+                sums += torch.nn.functional.one_hot(yz, C).double().T @ V
+            else:
+                sums.index_add_(0, yz, V)
+            sq += (V * V).sum(0)
+            cnt += torch.bincount(yl[ok], minlength=C).double()
+            bad += (~fin & ok[:, None]).sum(0)
+            bad_label += (~ok).sum()
+        return {"sums": sums, "sq": sq, "n": cnt, "bad": bad, "bad_label": bad_label}
+    sx, sxx, sxy = torch.zeros(d, **f64), torch.zeros(d, **f64), torch.zeros(d, **f64)
+    sy, syy, cnt = torch.zeros((), **f64), torch.zeros((), **f64), torch.zeros((), **f64)
+    for i0 in range(0, n, LABEL_HOST_CHUNK):
+        Xc = X[i0:i0 + LABEL_HOST_CHUNK].double()
+        yc = label[i0:i0 + LABEL_HOST_CHUNK]
+        ok = torch.isfinite(yc)
+        yy = torch.where(ok, yc - ys, torch.zeros_like(yc))
+        fin = torch.isfinite(Xc)
+        V = torch.where(fin & ok[:, None], Xc - sh_t, torch.zeros_like(Xc))
+        sx += V.sum(0)
+        sxx += (V * V).sum(0)
+        sxy += V.T @ yy
+        sy += yy.sum()
+        syy += (yy * yy).sum()
+        cnt += ok.sum()
+        bad += (~fin & ok[:, None]).sum(0)
+        bad_label += (~ok).sum()
+    return {"sx": sx, "sxx": sxx, "sxy": sxy, "sy": sy, "syy": syy, "n": cnt, "bad": bad, "bad_label": bad_label}
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
