@@ -283,6 +283,7 @@ def dict_encode(arr, device):
 # ----------------------------------------------------------- K16 partitioned hash operators (hashagg.hip)
 HP_MAX_ACC = 4
 HP_OPS = {"sum": 0, "min": 1, "max": 2, "count": 3, "last": 4}
+_PACK_MAX_COLS = 8   # hashagg.hip kMaxCols
 _PACK_DT = {torch.uint8: 0, torch.bool: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3, torch.int8: 4}
 _VAL_DT = {torch.float64: 0, torch.float32: 1, torch.int64: 2, torch.int32: 3, torch.uint8: 4, torch.bool: 4,
            torch.int16: 5, torch.int8: 6}
@@ -297,8 +298,17 @@ def _ptr_array(ts):
 def pack_keys(cols, n: int, dev) -> torch.Tensor:
     """K16 key words: cols = [(values 1-D integer tensor, valid bool tensor or None, lo, radix)] -> int64 [n] with
     word = sum_j code_j * prod_{l > j} radix_l, code = value - lo + 1 (null 0): equality is tuple equality and the
-    signed order is the lexicographic tuple order with nulls first.  The caller checks prod(radix) < 2^62."""
+    signed order is the lexicographic tuple order with nulls first.  The caller checks prod(radix) < 2^62.  Any
+    number of columns: the kernel packs up to 8 per launch, more go in stages."""
     import ctypes
+    if len(cols) > _PACK_MAX_COLS:
+        # the kernel takes 8 columns: pack the first 8, then that word (code = word: lo 1, no nulls, radix = the
+        # product of their radices) leads the next stage -- the same mixed-radix word as one pass would give
+        prod = 1
+        for c in cols[:_PACK_MAX_COLS]:
+            prod *= int(c[3])
+        head = pack_keys(cols[:_PACK_MAX_COLS], n, dev)
+        return pack_keys([(head, None, 1, prod)] + list(cols[_PACK_MAX_COLS:]), n, dev)
     vals = [v.contiguous() if v.dtype != torch.bool else v.contiguous().view(torch.uint8) for v, _, _, _ in cols]
     valids = [None if m is None else m.contiguous().view(torch.uint8) for _, m, _, _ in cols]
     k = len(cols)

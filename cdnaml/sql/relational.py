@@ -242,6 +242,11 @@ def _aggregate_native(batch: Batch, keys: List[str], aggs) -> Optional[Batch]:
         c = agg.x.eval(batch, ctx)
         simple = (not agg.distinct and c.values.dim() == 1 and c.values.dtype in R._VAL_DT and
                   not isinstance(c.dtype, T.StringType))
+        if simple and agg.kind in ("min", "max") and c.values.dtype == torch.int64 and c.values.numel():
+            # the table slots order values by their fp64 image: exact for int32 and narrower, and for longs up to
+            # 2^53; a long column that can exceed that takes the generic step (int64 reduction in _agg_one)
+            lo_, hi_ = (int(x) for x in torch.stack(list(torch.aminmax(c.values))).cpu().tolist())
+            simple = max(-lo_, hi_) <= (1 << 53)
         step = None
         if agg.kind == "first" and not agg.distinct:
             step = (name, "first", c, ())
@@ -398,6 +403,22 @@ def _agg_one(batch: Batch, agg, gid, G, first, ctx) -> ColumnData:
         ok = (r != fill)
         return ColumnData(torch.where(ok, r, torch.zeros_like(r)).to(torch.int32), c.dtype,
                           None if bool(ok.all()) else ok, c.dictionary)
+    if kind in ("min", "max") and c.values.dim() == 1 and c.values.dtype in _INT_DT:
+        # integral values reduce in int64: fp64 merges longs above 2^53 that differ in their low bits
+        xi = c.values.to(torch.int64)
+        info = torch.iinfo(torch.int64)
+        fill = info.max if kind == "min" else info.min
+        r = torch.full((G,), fill, dtype=torch.int64, device=dev)
+        r.scatter_reduce_(0, gid, torch.where(valid, xi, torch.full_like(xi, fill)),
+                          reduce="amin" if kind == "min" else "amax", include_self=True)
+        nn = torch.zeros(G, dtype=torch.int64, device=dev)
+        nn.index_add_(0, gid, valid.to(torch.int64))
+        nonempty = nn > 0
+        r = torch.where(nonempty, r, torch.zeros_like(r))
+        dt = c.dtype
+        tdt = dt.torch_dtype if isinstance(dt, (T.IntegralType, T.DateType, T.TimestampType, T.BooleanType)) \
+            else c.values.dtype
+        return ColumnData(r.to(tdt), dt, None if bool(nonempty.all()) else nonempty)
     x = c.values.to(torch.float64) if c.values.dim() == 1 else c.values.to(torch.float64)
     xz = torch.where(valid, x, torch.zeros_like(x))
     cnt = K.group_sum(None if c.valid is None else valid.to(torch.float64), gid, G)
@@ -412,10 +433,18 @@ def _agg_one(batch: Batch, agg, gid, G, first, ctx) -> ColumnData:
         s = _seg_sum(xz, gid, G)
         return ColumnData(s / cnt.clamp_min(1), T.DoubleType(), vnull)
     if kind in ("min", "max"):
+        # Spark orders NaN above +inf (as the K16 tables do): min skips NaN unless every non-null value of the
+        # group is NaN, max is NaN as soon as one is.  The reduction itself runs over the other values.
         fill = float("inf") if kind == "min" else float("-inf")
-        xv = torch.where(valid, x, torch.full_like(x, fill))
+        isnan = valid & torch.isnan(x)
+        xv = torch.where(valid & ~isnan, x, torch.full_like(x, fill))
         r = torch.full((G,), fill, dtype=torch.float64, device=dev)
         r.scatter_reduce_(0, gid, xv, reduce="amin" if kind == "min" else "amax", include_self=True)
+        nnan = torch.zeros((2, G), dtype=torch.int64, device=dev)      # NaN values, other values per group
+        nnan[0].index_add_(0, gid, isnan.to(torch.int64))
+        nnan[1].index_add_(0, gid, (valid & ~isnan).to(torch.int64))
+        tonan = (nnan[0] > 0) & (nnan[1] == 0) if kind == "min" else (nnan[0] > 0)
+        r = torch.where(tonan, torch.full_like(r, float("nan")), r)
         r = torch.where(nonempty, r, torch.zeros_like(r))
         dt = c.dtype
         if isinstance(dt, (T.IntegralType, T.DateType, T.TimestampType, T.BooleanType)):
