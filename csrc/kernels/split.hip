@@ -104,7 +104,10 @@ __global__ __launch_bounds__(kThreads) void split_scan_kernel(const SplitArgs a)
       l1 += hf[2 * b + 1];
       bool ok;
       const double g = gain_of(a, l0, l1, t0 - l0, t1 - l1, t0, t1, &ok);
-      if (ok && g == g && g != __builtin_inf() && g != -__builtin_inf() && g > best) {
+      // (a thread meets its keys out of order -- a feature's missing-right candidates before the next bin's and the
+      // next feature's missing-left ones -- so an equal gain with a lower key replaces the kept candidate)
+      if (ok && g == g && g != __builtin_inf() && g != -__builtin_inf() &&
+          (g > best || (g == best && f * a.B + b < bk))) {
         best = g;
         bk = f * a.B + b;
       }
@@ -168,10 +171,11 @@ __global__ __launch_bounds__(kThreads) void split_scan_kernel(const SplitArgs a)
 // split_scan_kernel walks a feature's B bins serially in one thread, so a level costs one thread's 2 x B-bin walk
 // whatever A is (~155 us per level at B = 256: 1.25 ms of a 24 ms boosting round).  Here a wave owns a feature
 // (lane l: bins [R l, R l + R)), 16 waves per node: lane prefix + wave scan, the same gain_of per candidate, and
-// the same winner as split_scan_kernel including its tie order -- thread t of that kernel walks features
-// t, t + 128, ... in (feature, bin, left-then-right) order and keeps the FIRST candidate of its best gain, then the
-// block keeps the lowest key among equal gains; the per-feature first candidates kept here reproduce both steps.
+// the same winner as split_scan_kernel including its tie order: the lowest key among the candidates of the best
+// gain -- per feature the lowest missing-left bin of that gain, else the lowest missing-right one (every
+// missing-left key is below every missing-right key), then the lowest key over the features.
 constexpr int kWaveMaxD = 4096;
+constexpr int kWaveRight = 512;  // candidate code: bin (< 256) | kWaveRight for a missing-right candidate
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -182,7 +186,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 template <int R>
 __global__ __launch_bounds__(1024) void split_scan_wave_kernel(const SplitArgs a) {
   __shared__ double s_fg[kWaveMaxD];  // per feature: best legal gain (-inf: none)
-  __shared__ int s_fc[kWaveMaxD];     // per feature: its first candidate of that gain, bin << 1 | missing-right
+  __shared__ int s_fc[kWaveMaxD];     // per feature: its lowest-key candidate of that gain (bin | kWaveRight)
   __shared__ double s_w[16], s_t0[16], s_t1[16], s_g[16];
   __shared__ int s_f[16], s_k[16];
   const int node = blockIdx.x;
@@ -230,7 +234,7 @@ __global__ __launch_bounds__(1024) void split_scan_wave_kernel(const SplitArgs a
         t1 = s_t1[i];
       }
   }
-  // pass 2: every legal threshold; per feature the best gain and its first candidate in the serial walk's order
+  // pass 2: every legal threshold; per feature the best gain and its candidate with the lowest key
   for (int f = wid; f < a.d; f += 16) {
     double best = -__builtin_inf();
     int code = 0x7FFFFFFF;
@@ -268,22 +272,23 @@ __global__ __launch_bounds__(1024) void split_scan_wave_kernel(const SplitArgs a
           const double l0 = e0 + p0[r], l1 = e1 + p1[r];
           bool ok;
           const double g = gain_of(a, l0, l1, t0 - l0, t1 - l1, t0, t1, &ok);
-          if (ok && g == g && g != __builtin_inf() && g != -__builtin_inf() && g > best) {
+          if (ok && g == g && g != __builtin_inf() && g != -__builtin_inf() &&
+              (g > best || (g == best && b < code))) {
             best = g;
-            code = b << 1;
+            code = b;
           }
           if (a.missing_bin && b >= 1) {
             const double q0 = l0 - m0, q1 = l1 - m1;
             const double g2 = gain_of(a, q0, q1, t0 - q0, t1 - q1, t0, t1, &ok);
             if (ok && g2 == g2 && g2 != __builtin_inf() && g2 != -__builtin_inf() && g2 > best) {
               best = g2;
-              code = (b << 1) | 1;
+              code = kWaveRight | b;
             }
           }
         }
       }
     }
-    // wave: the highest gain, the lowest code (the serial walk's first) among equal gains
+    // wave: the highest gain, the lowest code (= the lowest key of the feature) among equal gains
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const double og = __shfl_xor(best, o, 64);
@@ -307,16 +312,15 @@ __global__ __launch_bounds__(1024) void split_scan_wave_kernel(const SplitArgs a
     const double og = __shfl_xor(G, o, 64);
     G = og > G ? og : G;
   }
-  // split_scan_kernel's thread t (features t, t + 128, ...) keeps its first candidate of gain G; the block keeps the
-  // lowest key of those
+  // the lowest key among the features' candidates of gain G
   const int off2 = a.d * a.B;
   int key = 0x7FFFFFFF;
   if (G != -__builtin_inf() && threadIdx.x < 128) {
     for (int f = threadIdx.x; f < a.d; f += 128)
       if (s_fg[f] == G) {
         const int c = s_fc[f];
-        key = (c & 1) ? off2 + f * a.B + (c >> 1) : f * a.B + (c >> 1);
-        break;
+        const int k = (c & kWaveRight) ? off2 + f * a.B + (c & (kWaveRight - 1)) : f * a.B + c;
+        key = k < key ? k : key;
       }
   }
 #pragma unroll
