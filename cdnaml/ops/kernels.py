@@ -2083,16 +2083,22 @@ class MlpPrepared:
         return self._made[key]
 
 
-def _mlp_native_plan(X: torch.Tensor, layers):
-    """cdna_mlp_plan's answer for these operands (None: the host formulation) and X as the kernel takes it."""
-    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2 or X.shape[1] != layers[0]:
+def _row_plan(X: torch.Tensor, fn_name: str, nout: int, *args):
+    """The answer of a row-streaming kernel's plan function ``fn_name(X, n, ldx, *args, out[nout])`` for these
+    operands (None: the host formulation) and X as the kernel takes it: fp32 rows of unit stride."""
+    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2:
         return None, X
     X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
-    lay = np.asarray(layers, dtype=np.int32)
-    out = np.zeros(8, dtype=np.int64)
-    _lib.check(_lib.lib().cdna_mlp_plan(_ptr(X), X.shape[0], X.stride(0), lay.ctypes.data, len(lay),
-                                        out.ctypes.data), "cdna_mlp_plan")
+    out = np.zeros(nout, dtype=np.int64)
+    _lib.check(getattr(_lib.lib(), fn_name)(_ptr(X), X.shape[0], X.stride(0), *args, out.ctypes.data), fn_name)
     return (out if out[0] else None), X
+
+
+def _mlp_native_plan(X: torch.Tensor, layers):
+    if X.dim() != 2 or X.shape[1] != layers[0]:
+        return None, X
+    lay = np.asarray(layers, dtype=np.int32)
+    return _row_plan(X, "cdna_mlp_plan", 8, lay.ctypes.data, len(lay))
 
 
 def mlp_plan(X: torch.Tensor, layers) -> Dict[str, object]:
@@ -2269,14 +2275,7 @@ class FmPrepared:
 
 
 def _fm_native_plan(X: torch.Tensor, k: int, fit_linear: bool):
-    """cdna_fm_plan's answer for these operands (None: the host formulation) and X as the kernel takes it."""
-    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2:
-        return None, X
-    X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
-    out = np.zeros(10, dtype=np.int64)
-    _lib.check(_lib.lib().cdna_fm_plan(_ptr(X), X.shape[0], X.stride(0), X.shape[1], int(k), int(fit_linear),
-                                       out.ctypes.data), "cdna_fm_plan")
-    return (out if out[0] else None), X
+    return _row_plan(X, "cdna_fm_plan", 10, X.shape[-1], int(k), int(fit_linear))
 
 
 def fm_plan(X: torch.Tensor, k: int, fit_linear: bool = True) -> Dict[str, object]:
@@ -2405,14 +2404,7 @@ def aft_quantile_factors(probs, log_sigma: float) -> np.ndarray:
 
 
 def _aft_native_plan(X: torch.Tensor):
-    """cdna_aft_plan's answer for these operands (None: the host formulation) and X as the kernel takes it."""
-    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2:
-        return None, X
-    X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
-    out = np.zeros(6, dtype=np.int64)
-    _lib.check(_lib.lib().cdna_aft_plan(_ptr(X), X.shape[0], X.stride(0), X.shape[1], out.ctypes.data),
-               "cdna_aft_plan")
-    return (out if out[0] else None), X
+    return _row_plan(X, "cdna_aft_plan", 6, X.shape[-1])
 
 
 def aft_plan(X: torch.Tensor) -> Dict[str, object]:
@@ -2535,16 +2527,8 @@ LABEL_HOST_CHUNK = 1 << 18     # rows per pass of the host formulation
 
 
 def _label_native_plan(X: torch.Tensor, mode: int, C: int, K: int):
-    """cdna_label_stats_plan's answer for these operands (None: the host formulation), X as the kernel takes it and
-    the plan's constants (the COUNT table's LDS budget)."""
-    if not _native(X) or X.dtype != torch.float32 or X.dim() != 2:
-        return None, X
-    X = X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
-    out = np.zeros(8, dtype=np.int64)
-    C, K = min(int(C), 1 << 30), min(int(K), 1 << 30)
-    _lib.check(_lib.lib().cdna_label_stats_plan(_ptr(X), X.shape[0], X.stride(0), X.shape[1], int(mode), C, K,
-                                                out.ctypes.data), "cdna_label_stats_plan")
-    return (out if out[0] else None), X
+    return _row_plan(X, "cdna_label_stats_plan", 8, X.shape[-1], int(mode), min(int(C), 1 << 30),
+                     min(int(K), 1 << 30))
 
 
 def label_stats_plan(X: torch.Tensor, mode: int, C: int = 1, K: int = 1) -> Dict[str, object]:

@@ -8,11 +8,11 @@
 //   predict = exp(x.beta + b),   quantile_p = predict * exp(sigma log(-log(1 - p)))
 // The kernel works on the raw rows: the host passes beta already divided by the features' std.
 //
-// aft_step_kernel<MODE, VW>: 256 threads, 64-row tiles, the next tile of X prefetched in registers (K25's
-// scaffolding, symtile.h's RowTile).  The tile is row-major fp32 in LDS with the odd row stride kLD, columns d ..
-// zeroed once.  LDS: the tile (33024 B), fp64 coef [128], this tile's m [64], the tile rows' running loss, sum of m
-// and sum of dlogsigma [3][64], the quantile factors [16], the rows' bad counts (int [64]): 36480 B, four blocks per
-// CU of 160 KB (the registers of the STEP instantiations let three in, see aft_plan).
+// aft_step_kernel<MODE, VW>: 256 threads, 64-row tiles, the next tile of X prefetched in registers, the tile row-major
+// fp32 in LDS with the odd row stride kLD (rowblock.h's scaffolding: the row split, the tile and its pipeline).  LDS:
+// the tile (33024 B), fp64 coef [128], this tile's m [64], the tile rows' running loss, sum of m and sum of dlogsigma
+// [3][64], the quantile factors [16], the rows' bad counts (int [64]): 36480 B, four blocks per CU of 160 KB (the
+// registers of the STEP instantiations let three in, see aft_plan).
 //   x.beta: the four threads of a row take 32 columns each, in fp64 from the LDS tile, and add their partials with
 //     lane shuffles.  Thread q starts its quarter 8 q columns in (and wraps), so the 32 lanes of a half wave (8 rows x
 //     4 quarters; row stride 129 = 1 mod 32) read 32 different banks.  The same loop sums x * 0 in fp32: anything but
@@ -23,27 +23,23 @@
 //     gradient never multiplies a NaN by 0.  Rows past the end of the block's range are zeros in the tile and are
 //     never read from memory.
 //   gradient: thread (column tid & 127, row half tid >> 7) adds m_r x_rc over its 32 rows into one fp64 register for
-//     all the block's tiles (K25's c_i pattern: a wave reads 64 consecutive floats of a tile row).  At the end the
+//     all the block's tiles (a wave reads 64 consecutive floats of a tile row).  At the end the
 //     two halves fold through LDS and the block writes [dbeta (d) .. | sum m | sum dlogsigma | loss | bad] to its own
 //     workspace slot of kSlot doubles.
 //   PREDICT: exp(x.beta + b) per row, and with Q > 0 the [n][Q] quantiles in the same pass (the tile's predictions
 //     go through LDS so that the [64][Q] block is written in consecutive doubles).
-// aft_reduce_kernel: 16 threads per output value each sum a fixed stride of blocks, then the 16 in a fixed order, in
-// fp64.  No float atomics on global memory: reruns are bit-identical.
+// aft_reduce_kernel: the slots' sum over the blocks in a fixed order in fp64 (rowblock.h's sum_blocks).  No float
+// atomics on global memory: reruns are bit-identical.
 // Native range: fp32 rows, d <= 128, Q <= 16, any n, row stride and alignment.
 #include <cmath>
 
-#include "symtile.h"
+#include "rowblock.h"
 
 namespace {
 
-using namespace symtile;
+using namespace rowblock;
 
-constexpr int kRows = 64;
-constexpr int kMaxD = 128;
 constexpr int kMaxQ = 16;
-constexpr int kLD = kMaxD + 1;  // odd: the column reads of the gradient and the quarter reads of x.beta hit 32 banks
-constexpr int kXF = kRows * kLD;
 // fp64 words of LDS behind the tile: coef [kMaxD], per tile row m, loss, sum of m, sum of dlogsigma; the quantile
 // factors [kMaxQ]
 constexpr int kRedD = kMaxD + 4 * kRows;
@@ -78,8 +74,6 @@ __global__ __launch_bounds__(256) void aft_step_kernel(
   const int tid = threadIdx.x;
   const int d = pr.d, dv = d / VW, Q = pr.Q;
 
-  // zero the tile once: columns d .. are never written again
-  for (int i = tid; i < kXF; i += 256) xb[i] = 0.f;
   for (int i = tid; i < kRedD + kMaxQ; i += 256) {
     double v = 0.0;
     if (i < d) v = coef[i];
@@ -89,34 +83,24 @@ __global__ __launch_bounds__(256) void aft_step_kernel(
   if (tid < kRows) cnt[tid] = 0;
   double gacc = 0.0;  // dbeta of column tid & 127 over the row half tid >> 7, summed over the block's tiles
 
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   const int rr = tid >> 2, qq = tid & 3, bc = tid & (kMaxD - 1), bh = tid >> 7;
-  RowTile<VW> xt;
   double ltn = 0.0, dln = 0.0;
-
-  if (rb0 < rb1) {
-    xt.load(X, rb0, ldx, rb1 - rb0, tid, dv);
-    if (kTrain && rb0 + rr < rb1) {
-      ltn = logt[rb0 + rr];
-      dln = cens[rb0 + rr];
+  // the row's log t and censor travel with its tile
+  const auto side = [&](int64_t t, int i) {
+    if (kTrain && t + (i >> 2) < rb1) {
+      ltn = logt[t + (i >> 2)];
+      dln = cens[t + (i >> 2)];
     }
-  }
+  };
+  TileStream<VW> ts;
+  ts.begin(xb, kXF, X, ldx, rb0, rb1, dv, tid, side);
   for (int64_t t0 = rb0; t0 < rb1; t0 += kRows) {
-    const bool more = t0 + kRows < rb1;
     const bool valid = t0 + rr < rb1;
     const double lt = ltn, dl = dln;
-    __syncthreads();  // every wave is past its reads of the previous tile (and the zeroing, at first)
-    xt.store(xb, kLD, tid, dv, [](int, int, float x) { return x; });
-    if (more) {
-      xt.load(X, t0 + kRows, ldx, rb1 - (t0 + kRows), tid, dv);
-      if (kTrain && t0 + kRows + rr < rb1) {
-        ltn = logt[t0 + kRows + rr];
-        dln = cens[t0 + kRows + rr];
-      }
-    }
-    __syncthreads();  // tile complete
+    ts.put(xb, tid);
+    ts.fetch(t0, tid, side);
 
     // x.beta, four threads per row, and the features' finiteness
     float* xq = xb + rr * kLD + 32 * qq;
@@ -215,26 +199,15 @@ __global__ __launch_bounds__(256) void aft_step_kernel(
 __global__ __launch_bounds__(256) void aft_reduce_kernel(const double* __restrict__ ws, int nblk, int d,
                                                          double* __restrict__ out) {
   __shared__ double red[16][16];
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int idx = blockIdx.x * 16 + el;
+  const int idx = blockIdx.x * 16 + (threadIdx.x & 15);
   const bool ok = idx < d + 4;
   const int src = idx < d ? idx : kMaxD + (idx - d);
-  double s = 0.0;
-  if (ok)
-    for (int b = part; b < nblk; b += 16) s += ws[(int64_t)b * kSlot + src];
-  red[part][el] = s;
-  __syncthreads();
-  if (part != 0 || !ok) return;
-  double t = 0.0;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) t += red[q][el];
-  out[idx] = t;
+  const double t = sum_blocks(red, nblk, ok, [&](int b) { return ws[(int64_t)b * kSlot + src]; });
+  if (threadIdx.x < 16 && ok) out[idx] = t;
 }
 
-struct AftPlan {
+struct AftPlan : RowSplit {
   bool native;
-  int nblk;
-  int64_t rows_per_block;
 };
 
 // One round of resident blocks on the 256 CUs: three per CU by registers (the float4 STEP instantiation holds 142 per
@@ -243,11 +216,7 @@ AftPlan aft_plan(int64_t n, int d) {
   AftPlan pl{};
   pl.native = n >= 1 && d >= 1 && d <= kMaxD;
   if (!pl.native) return pl;
-  int64_t nb = (n + 1023) / 1024;
-  if (nb > 3 * 256) nb = 3 * 256;
-  const int64_t rpb = ((n + nb - 1) / nb + kRows - 1) / kRows * kRows;
-  pl.rows_per_block = rpb;
-  pl.nblk = (int)((n + rpb - 1) / rpb);  // every block has rows
+  static_cast<RowSplit&>(pl) = split_rows(n, 3 * 256);
   return pl;
 }
 

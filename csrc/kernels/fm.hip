@@ -6,8 +6,9 @@
 //   squared loss (raw - y)^2 with m = 2 (raw - y); logistic loss log1p(exp(-+raw)) with m = sigmoid(raw) - y
 //   db = m,  dw_i = m x_i,  dv_if = m (s_f x_i - v_if x_i^2)
 //
-// fm_step_kernel: 256 threads, 64-row tiles, the next tile of X prefetched in registers (K24's scaffolding).  The X
-// tile is row-major fp32 in LDS with the odd row stride kLD, the [64][KC] product buffer with the odd stride kSD.
+// fm_step_kernel: 256 threads, 64-row tiles, the next tile of X prefetched in registers (rowblock.h's scaffolding:
+// the row split, the tile and its pipeline).  The X tile is row-major fp32 in LDS with the odd row stride kLD, the
+// [64][KC] product buffer with the odd stride kSD.
 //   X V: w is carried as column k of V (KC = k + 1 columns with linear weights), so S = X [V | w] gives s and w.x
 //     from one product on v_mfma_f32_32x32x2_f32.  Wave w forms the 32-row block (w & 1) of column block (w >> 1);
 //     its B operand is consecutive floats of the zero-padded fp32 table [d up to 2][KC up to 32] the host prepares.
@@ -20,9 +21,9 @@
 //     wave); both operands are consecutive floats of one LDS row (symtile.h's mfma_rows pattern with two buffers).
 //     fp32 accumulators in registers for kFoldTiles tiles, then folded into the block's fp64 slab (each element
 //     owned by one lane).  c_i = sum_r m_r x_ri^2: fp64 column sums, one thread per (column, row half).
-// fm_reduce_kernel: slabs, column sums, loss, sum of m and count of the blocks in a fixed order in fp64, straight
-// into the flat layout: dV_if = G_if - v_if c_i, dw_i = G_ik, db = sum m.  No float atomics on global memory: reruns
-// are bit-identical.
+// fm_reduce_kernel: slabs, column sums, loss, sum of m and count of the blocks in a fixed order in fp64 (rowblock.h's
+// sum_blocks), straight into the flat layout: dV_if = G_if - v_if c_i, dw_i = G_ik, db = sum m.  No float atomics on
+// global memory: reruns are bit-identical.
 // Row selection (miniBatchFraction): row r is in when philox_uniform(seed, row_offset + r, stream) < frac, drawn here.
 // Native range: d <= 128, k <= 32.
 #include "symtile.h"
@@ -31,12 +32,9 @@ namespace {
 
 using namespace symtile;
 
-constexpr int kRows = 64;
-constexpr int kMaxD = 128;
 constexpr int kMaxK = 32;
-constexpr int kLD = kMaxD + 1;       // odd: the A operand's 32 rows hit 32 banks
-constexpr int kSD = 2 * 32 + 1;      // the product buffer: up to 2 column blocks
-constexpr int kXF = kRows * kLD, kSF = kRows * kSD;  // floats of the two buffers
+constexpr int kSD = 2 * 32 + 1;      // the product buffer: up to 2 column blocks, odd like kLD
+constexpr int kSF = kRows * kSD;     // its floats
 constexpr int kFoldTiles = 8;        // 512 rows of fp32 accumulation between folds into the fp64 slab
 // fp64 words of LDS behind the two buffers: u [kMaxD], per tile row m, loss, sum of m; then the rows' counts (int).
 // 52.5 KB in all: three blocks share a CU's 160 KB
@@ -106,8 +104,6 @@ __global__ __launch_bounds__(256) void fm_step_kernel(
   const int d = sh.d, dv = d / VW, k = sh.k;
   const int NT = sh.Td * sh.Tc;
 
-  // zero the buffers once: columns d .. of the X tile are never written again (column d is read when d is odd)
-  for (int i = tid; i < kXF + kSF; i += 256) xb[i] = 0.f;
   for (int i = tid; i < kRedD; i += 256) red[i] = i < kMaxD ? u[i] : 0.0;
   if (tid < kRows) cnt[tid] = 0;
   double cacc = 0.0;  // c_i of column tid & 127 over the row half tid >> 7, summed over the block's tiles
@@ -118,19 +114,19 @@ __global__ __launch_bounds__(256) void fm_step_kernel(
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[s][e] = 0.f;
 
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   double* myws = ws != nullptr ? ws + (int64_t)blockIdx.x * block_doubles(NT) : nullptr;
-  RowTile<VW> xt;
   double yv = 0.0;
   bool first = true;
   int pending = 0;
-
-  if (rb0 < rb1) {
-    xt.load(X, rb0, ldx, rb1 - rb0, tid, dv);
-    if (kTrain && rb0 + (tid >> 2) < rb1) yv = y[rb0 + (tid >> 2)];
-  }
+  // the row's y travels with its tile
+  const auto side = [&](int64_t t, int i) {
+    if (kTrain && t + (i >> 2) < rb1) yv = y[t + (i >> 2)];
+  };
+  TileStream<VW> ts;
+  // both buffers are zeroed: column d of the X tile is read when d is odd
+  ts.begin(xb, kXF + kSF, X, ldx, rb0, rb1, dv, tid, side);
   for (int64_t t0 = rb0; t0 < rb1; t0 += kRows) {
     const bool more = t0 + kRows < rb1;
     int tl = tid;
@@ -138,13 +134,8 @@ __global__ __launch_bounds__(256) void fm_step_kernel(
     const int lane = tl & 63, rr = tl >> 2, qq = tl & 3, bc = tl & (kMaxD - 1), bh = tl >> 7;
     const bool valid = t0 + rr < rb1;
     const double lab = yv;
-    __syncthreads();  // every wave is past its reads of both buffers for the previous tile (and the zeroing, at first)
-    xt.store(xb, kLD, tl, dv, [](int, int, float x) { return x; });
-    if (more) {
-      xt.load(X, t0 + kRows, ldx, rb1 - (t0 + kRows), tl, dv);
-      if (kTrain && t0 + kRows + rr < rb1) yv = y[t0 + kRows + rr];
-    }
-    __syncthreads();  // tile complete
+    ts.put(xb, tl);
+    ts.fetch(t0, tl, side);
 
     // S = X [V | w]
     {
@@ -295,17 +286,15 @@ __global__ __launch_bounds__(256) void fm_step_kernel(
   }
 }
 
-// One block of 256 threads per 16 output values: 16 threads per value each sum a fixed stride of blocks (a slab
-// element together with the column sum c_i it is corrected by), then a fixed-order sum; the value goes to its
-// place in out [P + 2]: the flat gradient, the loss, the count.
+// One block of 256 threads per 16 output values, summed over the blocks (a slab element together with the column sum
+// c_i it is corrected by); the value goes to its place in out [P + 2]: the flat gradient, the loss, the count.
 __global__ __launch_bounds__(256) void fm_reduce_kernel(const double* __restrict__ ws, int nblk, const FmShape sh,
                                                         const float* __restrict__ tab, double* __restrict__ out) {
   __shared__ double red[2][16][16];
   const int NT = sh.Td * sh.Tc;
   const int64_t stride = block_doubles(NT);
   const int64_t slabs = (int64_t)NT * 1024, total = slabs + 3;
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int64_t idx = (int64_t)blockIdx.x * 16 + el;
+  const int64_t idx = (int64_t)blockIdx.x * 16 + (threadIdx.x & 15);
   const bool ok = idx < total;
   const bool slab = idx < slabs;
   int i = 0, f = 0;
@@ -318,22 +307,13 @@ __global__ __launch_bounds__(256) void fm_reduce_kernel(const double* __restrict
   } else {
     src = slabs + kMaxD + (idx - slabs);
   }
-  double s = 0.0, c = 0.0;
-  if (ok)
-    for (int b = part; b < nblk; b += 16) {
-      s += ws[(int64_t)b * stride + src];
-      if (slab) c += ws[(int64_t)b * stride + slabs + i];
-    }
-  red[0][part][el] = s;
-  red[1][part][el] = c;
-  __syncthreads();
-  if (part != 0 || !ok) return;
-  double t = 0.0, ct = 0.0;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    t += red[0][q][el];
-    ct += red[1][q][el];
-  }
+  double tt[2];  // the value, and for a slab element the column sum c_i
+  sum_blocks(red, nblk, ok, tt, [&](int b, double* s) {
+    s[0] += ws[(int64_t)b * stride + src];
+    if (slab) s[1] += ws[(int64_t)b * stride + slabs + i];
+  });
+  if (threadIdx.x >= 16 || !ok) return;
+  const double t = tt[0], ct = tt[1];
   if (slab) {
     if (i >= sh.d) return;
     if (f < sh.k)
@@ -348,11 +328,9 @@ __global__ __launch_bounds__(256) void fm_reduce_kernel(const double* __restrict
   }
 }
 
-struct FmPlan {
+struct FmPlan : RowSplit {
   bool native;
   int slots;  // gradient tiles per wave of the STEP instantiation
-  int nblk;
-  int64_t rows_per_block;
   size_t lds;
 };
 
@@ -364,13 +342,7 @@ FmPlan fm_plan(int64_t n, int d, int k, int fit_linear, bool step = true) {
   if (!pl.native) return pl;
   const FmShape sh = make_shape(d, k, fit_linear, 0, 0);
   pl.slots = sh.Td * sh.Tc <= 4 ? 1 : 2;
-  int64_t nb = (n + 1023) / 1024;
-  const int64_t cap = step && pl.slots == 2 ? 2 * 256 : 3 * 256;
-  if (nb > cap) nb = cap;
-  if (nb < 1) nb = 1;
-  const int64_t rpb = ((n + nb - 1) / nb + kRows - 1) / kRows * kRows;
-  pl.rows_per_block = rpb;
-  pl.nblk = (int)((n + rpb - 1) / rpb);  // every block has rows
+  static_cast<RowSplit&>(pl) = split_rows(n, step && pl.slots == 2 ? 2 * 256 : 3 * 256);
   pl.lds = (size_t)(kXF + kSF) * 4 + (size_t)kRedD * 8 + kRows * 4;
   return pl;
 }

@@ -32,8 +32,7 @@ namespace {
 using namespace symtile;
 
 constexpr double kEps = 1e-16;
-constexpr int kRows = 64;
-constexpr int kMaxD = 128;  // d + 2 <= kMaxD
+// kRows, kMaxD: rowblock.h's 64-row tile and its 128 columns; d + 2 <= kMaxD
 
 enum { kGaussian = 0, kBinomial = 1, kPoisson = 2, kGamma = 3, kTweedie = 4 };
 enum { kIdentity = 0, kLog = 1, kInverse = 2, kLogit = 3, kProbit = 4, kCloglog = 5, kSqrt = 6, kPower = 7 };
@@ -188,9 +187,8 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : 1) void glm_step_kernel(
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   const int rr = tid >> 2, q = tid & 3;  // row phase: 4 threads per row
   vec_t v[kNI];
   double yv = 0.0, wv = 0.0, ov = 0.0;
@@ -296,27 +294,17 @@ __global__ __launch_bounds__(256, VW == 4 ? 2 : 1) void glm_step_kernel(
   if (tid < 4) spart[(int64_t)blockIdx.x * 4 + tid] = ((red[tid] + red[4 + tid]) + red[8 + tid]) + red[12 + tid];
 }
 
-// Blocks 0 .. gridDim.x - 2: partial [nblk][npairs][1024] -> G (symmetric fill), 16 threads per element each
-// summing a fixed stride of blocks, then a fixed-order sum (symtile::reduce_slabs).  Last block: the scalars,
-// spart [nblk][4] -> stats[4], the same way.
+// Blocks 0 .. gridDim.x - 2: partial [nblk][npairs][1024] -> G (symmetric fill), symtile::reduce_slabs.  Last block:
+// the scalars, spart [nblk][4] -> stats[4]; both in the fixed order of rowblock.h's sum_blocks.
 __global__ __launch_bounds__(256) void glm_reduce_kernel(const float* __restrict__ partial, int nblk, int npairs,
                                                          int T, int D, double* __restrict__ G,
                                                          const double* __restrict__ spart,
                                                          double* __restrict__ stats) {
   __shared__ double red[16][16];
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
   if (blockIdx.x == gridDim.x - 1) {
-    double s = 0.0;
-    if (el < 4)
-      for (int b = part; b < nblk; b += 16) s += spart[(int64_t)b * 4 + el];
-    red[part][el] = s;
-    __syncthreads();
-    if (part == 0 && el < 4) {
-      double t = 0.0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) t += red[k][el];
-      stats[el] = t;
-    }
+    const int el = threadIdx.x & 15;  // < 4: a scalar
+    const double t = sum_blocks(red, nblk, el < 4, [&](int b) { return spart[(int64_t)b * 4 + el]; });
+    if (threadIdx.x < 4) stats[el] = t;
     return;
   }
   reduce_slabs(red, partial, npairs, nblk, npairs, [T](int p, int& I, int& J) { pair_ij(p, T, I, J); }, D, G,

@@ -35,8 +35,7 @@ namespace {
 
 using namespace symtile;
 
-constexpr int kRows = 64;
-constexpr int kMaxD = 128;  // d + 1 <= kMaxD
+// kRows, kMaxD: rowblock.h's 64-row tile and its 128 columns; d + 1 <= kMaxD
 constexpr int kMaxK = 32;
 constexpr double kGmmEps = 2.220446049250313e-16;  // 2^-52, Spark's EPSILON
 
@@ -63,9 +62,8 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(
   // zero the tile once: columns d .. LD - 1 are never written again (column d is read when d is odd)
   for (int i = tid; i < kRows * LD; i += 256) tile[i] = 0.f;
 
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   const int rr = tid >> 2, qq = tid & 3;  // row phase: 4 threads per row
   RowTile<VW> xt;
   double wv = 0.0;

@@ -152,9 +152,8 @@ __global__ __launch_bounds__(256) void gram_bf16_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[p][e] = 0.f;
   typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   const int half = lane >> 5;
   for (int64_t t0 = rb0; t0 < rb1; t0 += 64) {
     __syncthreads();
@@ -239,9 +238,8 @@ __global__ __launch_bounds__(256) void gram_bf16s_kernel(const float* __restrict
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   float4 v[NI][8];
   float yv = 0.f;
 // next tile's rows -> registers (rows past rb1 load the shift, i.e. become 0)
@@ -367,9 +365,8 @@ __global__ __launch_bounds__(256) void gram_bf16d_kernel(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, half = lane >> 5;
   const int d4 = d >> 2;
   const int xchunks = d >> 2;                      // 64 rows x d floats = d / 4 chunks of 1 KB (d % 4 == 0)
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   const int ntiles = rb0 < rb1 ? (int)((rb1 - rb0 + kDRows - 1) / kDRows) : 0;
   const char* xend = reinterpret_cast<const char*>(X + n * d);
   // one DMA round: this wave's kCPW chunks of tile `ti` into stage `ti % kDStages` (always kCPW instructions)

@@ -6,8 +6,9 @@
 // a_{l+1} = sigmoid(z_l) (l < L-1), loss = logsumexp(z_{L-1}) - z_{L-1}[label], delta_{L-1} = softmax - onehot,
 // delta_{l-1} = (W_lᵀ delta_l) a_l (1 - a_l), dW_l = sum_rows delta_l a_lᵀ, db_l = sum_rows delta_l.
 //
-// mlp_step_kernel: 256 threads, 64-row tiles, the next tile of X prefetched in registers.  Buffer l of LDS holds
-// the tile's a_l, row-major fp32 with the odd row stride kLD; the logits take buffer L.  Every matmul is
+// mlp_step_kernel: 256 threads, 64-row tiles, the next tile of X prefetched in registers (rowblock.h's scaffolding:
+// the row split, the tile and its pipeline).  Buffer l of LDS holds the tile's a_l, row-major fp32 with the odd row
+// stride kLD; the logits take buffer L.  Every matmul is
 // v_mfma_f32_32x32x2_f32:
 //   forward / backward (layer_mm): wave w forms the 32-row block (w & 1) of Y = S M for the column blocks (w >> 1) and
 //     (w >> 1) + 2; lane l's A operand at k-step m is S[32 rb + (l & 31)][m + (l >> 5)] (odd stride: 32 rows hit 32
@@ -21,8 +22,9 @@
 //     LDS row (symtile.h's mfma_rows pattern with two different buffers).  fp32 accumulators in registers for
 //     kFoldTiles tiles, then folded into the block's fp64 slab (each element owned by one lane: plain load, add,
 //     store).  db_l: column sums of the delta buffer, fp32 over 32 rows, fp64 across tiles.
-// mlp_reduce_kernel: slabs, bias sums and loss partials of the blocks in a fixed order in fp64, scattered into Spark's
-// flat layout (W_l column-major [out][in], then b_l).  No float atomics on global memory: reruns are bit-identical.
+// mlp_reduce_kernel: slabs, bias sums and loss partials of the blocks in a fixed order in fp64 (sum_blocks), scattered
+// into Spark's flat layout (W_l column-major [out][in], then b_l).  No float atomics on global memory: reruns are
+// bit-identical.
 // SLOTS = 0 is PREDICT: the forward half and the top, writing raw, prob and pred.
 // Native range: every width <= 128, 1 <= L <= 3 affine layers, 2 <= classes.
 #include "symtile.h"
@@ -31,13 +33,11 @@ namespace {
 
 using namespace symtile;
 
-constexpr int kRows = 64;
-constexpr int kMaxW = 128;
+constexpr int kMaxW = kMaxD;
 constexpr int kMaxL = 3;
-// LDS row stride of every buffer: odd (the A operand's 32 rows hit 32 banks) and a constant, so that the epilogues'
-// and the gradient's LDS addresses are one register plus an immediate
-constexpr int kLD = kMaxW + 1;
-constexpr int kBuf = kRows * kLD;  // floats per buffer
+// every buffer is a tile of rowblock.h: its row stride kLD is odd (the A operand's 32 rows hit 32 banks) and a
+// constant, so that the epilogues' and the gradient's LDS addresses are one register plus an immediate
+constexpr int kBuf = kXF;  // floats per buffer
 constexpr int kFoldTiles = 8;  // 512 rows of fp32 accumulation between folds into the fp64 slab
 
 enum { kStep = 0, kPredict = 1 };
@@ -166,9 +166,6 @@ __global__ __launch_bounds__(256) void mlp_step_kernel(
   const int C = pick(net.w, L);
   const int NT = net.tile0[kMaxL];
 
-  // zero the buffers once: columns d .. of buffer 0 are never written again (column d is read when d is odd)
-  for (int i = tid; i < net.lds_floats; i += 256) buf[i] = 0.f;
-
   // this wave's gradient tiles are wid, wid + 4, ..: tile wid + 4 s accumulates in acc[s]
   f32x16 acc[NS];
 #pragma unroll
@@ -176,12 +173,10 @@ __global__ __launch_bounds__(256) void mlp_step_kernel(
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[s][e] = 0.f;
 
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   // top: 4 threads per row, row tid >> 2; bias sums: column tid & 127 of the row half tid >> 7
   double* myws = ws != nullptr ? ws + (int64_t)blockIdx.x * block_doubles(NT) : nullptr;
-  RowTile<VW> xt;
   int yv = 0;
   // the block's running fp64 sums live in LDS, each entry touched by one thread until the end: db_l[column] per row
   // half, the loss per tile row
@@ -194,10 +189,13 @@ __global__ __launch_bounds__(256) void mlp_step_kernel(
   bool first = true;
   int pending = 0;
 
-  if (rb0 < rb1) {
-    xt.load(X, rb0, ldx, rb1 - rb0, tid, dv);
-    if (kTrain && rb0 + (tid >> 2) < rb1) yv = y[rb0 + (tid >> 2)];
-  }
+  // the row's label travels with its tile
+  const auto side = [&](int64_t t, int i) {
+    if (kTrain && t + (i >> 2) < rb1) yv = y[t + (i >> 2)];
+  };
+  TileStream<VW> ts;
+  // every buffer is zeroed: column d of buffer 0 is read when d is odd
+  ts.begin(buf, net.lds_floats, X, ldx, rb0, rb1, dv, tid, side);
   for (int64_t t0 = rb0; t0 < rb1; t0 += kRows) {
     const bool more = t0 + kRows < rb1;
     int tl = tid;  // this tile's copy of the thread index (see opaque), and what the phases derive from it
@@ -205,13 +203,8 @@ __global__ __launch_bounds__(256) void mlp_step_kernel(
     const int lane = tl & 63, rr = tl >> 2, qq = tl & 3, bc = tl & (kMaxW - 1), bh = tl >> 7;
     const bool valid = t0 + rr < rb1;
     const int lab = yv;
-    __syncthreads();  // every wave is past its reads of buffer 0 for the previous tile (and the zeroing, at first)
-    xt.store(buf, kLD, tl, dv, [](int, int, float x) { return x; });
-    if (more) {
-      xt.load(X, t0 + kRows, ldx, rb1 - (t0 + kRows), tl, dv);
-      if (kTrain && t0 + kRows + rr < rb1) yv = y[t0 + kRows + rr];
-    }
-    __syncthreads();  // tile complete
+    ts.put(buf, tl);
+    ts.fetch(t0, tl, side);
 
     // forward
 #pragma unroll
@@ -354,26 +347,18 @@ __global__ __launch_bounds__(256) void mlp_step_kernel(
   }
 }
 
-// One block of 256 threads per 16 values of a block's workspace: 16 threads per value each sum a fixed stride of
-// blocks, then a fixed-order sum; the value goes to its place in out [P + 1]: the flat gradient, then the loss.
+// One block of 256 threads per 16 values of a block's workspace, summed over the blocks; the value goes to its place
+// in out [P + 1]: the flat gradient, then the loss.
 __global__ __launch_bounds__(256) void mlp_reduce_kernel(const double* __restrict__ ws, int nblk, const MlpNet net,
                                                          double* __restrict__ out) {
   __shared__ double red[16][16];
   const int NT = net.tile0[kMaxL];
   const int64_t stride = block_doubles(NT);
   const int64_t total = (int64_t)NT * 1024 + kMaxL * kMaxW + 1;
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int64_t idx = (int64_t)blockIdx.x * 16 + el;
+  const int64_t idx = (int64_t)blockIdx.x * 16 + (threadIdx.x & 15);
   const bool ok = idx < total;
-  double s = 0.0;
-  if (ok)
-    for (int b = part; b < nblk; b += 16) s += ws[(int64_t)b * stride + idx];
-  red[part][el] = s;
-  __syncthreads();
-  if (part != 0 || !ok) return;
-  double t = 0.0;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) t += red[q][el];
+  const double t = sum_blocks(red, nblk, ok, [&](int b) { return ws[(int64_t)b * stride + idx]; });
+  if (threadIdx.x >= 16 || !ok) return;
   if (idx < (int64_t)NT * 1024) {
     const int tile = (int)(idx >> 10), e = (int)(idx & 1023);
     int l = 0;
@@ -398,11 +383,9 @@ __global__ __launch_bounds__(256) void mlp_reduce_kernel(const double* __restric
   }
 }
 
-struct MlpPlan {
+struct MlpPlan : RowSplit {
   bool native;
   int slots;  // gradient tiles per wave of the STEP instantiation
-  int nblk;
-  int64_t rows_per_block;
   size_t lds;
 };
 
@@ -417,12 +400,7 @@ MlpPlan mlp_plan(int64_t n, const int* layers, int nl) {
   const int per_wave = (net.tile0[net.L] + 3) / 4;
   for (int s : kSlotSteps)
     if (pl.slots == 0 && per_wave <= s) pl.slots = s;
-  int64_t nb = (n + 1023) / 1024;
-  if (nb > 1024) nb = 1024;
-  if (nb < 1) nb = 1;
-  const int64_t rpb = ((n + nb - 1) / nb + kRows - 1) / kRows * kRows;
-  pl.rows_per_block = rpb;
-  pl.nblk = (int)((n + rpb - 1) / rpb);  // every block has rows
+  static_cast<RowSplit&>(pl) = split_rows(n, 1024);
   pl.lds = (size_t)net.lds_floats * 4 + (size_t)(2 * kMaxL * kMaxW + kRows) * 8;
   return pl;
 }

@@ -10,12 +10,11 @@
 // Every mode also counts bad[d], the bad cells per feature: a bad cell adds nothing to its feature's statistics.  A row
 // whose label is bad (a code outside 0 .. C-1, a non-finite y) is never accumulated and is counted in bad_label.
 //
-// label_stats_kernel<MODE, VW>: K26's scaffolding (aft.hip) -- 256 threads, 64-row tiles, the next tile of X
-// prefetched in registers (symtile.h's RowTile), a row-major fp32 LDS tile with the odd row stride kLD whose columns
-// d .. are zeroed once; rows past the end of the block's range are never read from memory (they are zeros in the tile
-// and their label slot says "skip").  The thread that owns column tid & 127 and row half tid >> 7 in K26's gradient
-// loop owns that column's statistics here: a wave reads 64 consecutive floats of one tile row, and all its lanes
-// share the row's label.
+// label_stats_kernel<MODE, VW>: rowblock.h's scaffolding -- 256 threads, 64-row tiles, the next tile of X prefetched
+// in registers, a row-major fp32 LDS tile with the odd row stride kLD whose columns d .. are zeroed once; rows past
+// the end of the block's range are never read from memory (they are zeros in the tile and their label slot says
+// "skip").  Thread (column tid & 127, row half tid >> 7) owns that column's statistics: a wave reads 64 consecutive
+// floats of one tile row, and all its lanes share the row's label.
 //   COUNT: a per-block LDS table of u32 cells cell[(k * C + y) * pitch + c] with the column innermost and an odd
 //     pitch (d | 1): the lanes of a wave share y and differ in c and k, so they spread over the banks (a [c][k][y]
 //     layout puts every lane in one bank whenever K C is a multiple of 64).  LDS integer atomics (two threads own a
@@ -28,23 +27,19 @@
 //   The label statistics (n_c; sum (y - ys), its square and the count; bad_label) belong to the 64 threads that load the
 //   tile's labels.
 // CLASS and REGRESS write one workspace slot per block (all 128 columns: the ones past d hold zeros) and
-// label_reduce_kernel sums the slots in a fixed order in fp64.  No float atomics on global memory: reruns are
-// bit-identical.
+// label_reduce_kernel sums the slots in a fixed order in fp64 (rowblock.h's sum_blocks).  No float atomics on global
+// memory: reruns are bit-identical.
 // Native range: fp32 rows, 1 <= d <= 128, any n >= 1, row stride and alignment; CLASS: 2 <= C <= 32; COUNT: K, C >= 1
 // with K C (d | 1) 4 <= kCountBudget.
 #include <cmath>
 
-#include "symtile.h"
+#include "rowblock.h"
 
 namespace {
 
-using namespace symtile;
+using namespace rowblock;
 
-constexpr int kRows = 64;
-constexpr int kMaxD = 128;
-constexpr int kMaxC = 32;       // CLASS
-constexpr int kLD = kMaxD + 1;  // odd: the column reads hit 64 different banks
-constexpr int kXF = kRows * kLD;
+constexpr int kMaxC = 32;  // CLASS
 // the COUNT table's LDS budget: with the 33 KB tile a block stays under the 160 KB of a CU (one block per CU at the
 // budget; smaller tables let up to four in)
 constexpr size_t kCountBudget = 96 * 1024;
@@ -86,20 +81,16 @@ __global__ __launch_bounds__(256) void label_stats_kernel(
   const int tid = threadIdx.x;
   const int d = pr.d, dv = d / VW, C = pr.C;
 
-  // zero the tile once: columns d .. are never written again
-  for (int i = tid; i < kXF; i += 256) xb[i] = 0.f;
   if (tid < kMaxC) ncls[tid] = 0u;
   if (MODE == kCount)
     for (int i = tid; i < pr.K * C * pr.pitch; i += 256) cell[i] = 0u;
   if (MODE == kClass)
     for (int i = tid; i < 2 * C * kMaxD; i += 256) tab[i] = 0.0;
 
-  const int64_t rb0 = (int64_t)blockIdx.x * rows_per_block;
-  int64_t rb1 = rb0 + rows_per_block;
-  if (rb1 > n) rb1 = n;
+  int64_t rb0, rb1;
+  block_rows(rows_per_block, n, rb0, rb1);
   const int bc = tid & (kMaxD - 1), bh = tid >> 7;
   const double sh = MODE != kCount && bc < d ? shift[bc] : 0.0;
-  RowTile<VW> xt;
   int labn = -1;
   double yn = 0.0;
   // the column's statistics over the row half, summed over the block's tiles
@@ -109,17 +100,17 @@ __global__ __launch_bounds__(256) void label_stats_kernel(
   double sy = 0.0, syy = 0.0;
   unsigned int rows_ok = 0u, badl = 0u;
 
-  if (rb0 < rb1) {
-    xt.load(X, rb0, ldx, rb1 - rb0, tid, dv);
-    if (tid < kRows && rb0 + tid < rb1) {
-      if (MODE == kRegress) yn = yin[rb0 + tid];
-      else labn = codes[rb0 + tid];
+  // the tile rows' labels travel with the tile, in its first 64 threads
+  const auto side = [&](int64_t t, int i) {
+    if (i < kRows && t + i < rb1) {
+      if (MODE == kRegress) yn = yin[t + i];
+      else labn = codes[t + i];
     }
-  }
+  };
+  TileStream<VW> ts;
+  ts.begin(xb, kXF, X, ldx, rb0, rb1, dv, tid, side);
   for (int64_t t0 = rb0; t0 < rb1; t0 += kRows) {
-    const bool more = t0 + kRows < rb1;
-    __syncthreads();  // every wave is past its reads of the previous tile (and the zeroing, at first)
-    xt.store(xb, kLD, tid, dv, [](int, int, float x) { return x; });
+    ts.put(xb, tid);
     if (tid < kRows) {
       const bool valid = t0 + tid < rb1;
       bool ok;
@@ -138,14 +129,7 @@ __global__ __launch_bounds__(256) void label_stats_kernel(
       rows_ok += ok ? 1u : 0u;
       badl += valid && !ok ? 1u : 0u;
     }
-    if (more) {
-      xt.load(X, t0 + kRows, ldx, rb1 - (t0 + kRows), tid, dv);
-      if (tid < kRows && t0 + kRows + tid < rb1) {
-        if (MODE == kRegress) yn = yin[t0 + kRows + tid];
-        else labn = codes[t0 + kRows + tid];
-      }
-    }
-    __syncthreads();  // tile and labels complete
+    ts.fetch(t0, tid, side);  // tile and labels complete
 
     if (bc < d) {
       const float* xc = xb + (32 * bh) * kLD + bc;
@@ -254,30 +238,19 @@ __global__ __launch_bounds__(256) void label_stats_kernel(
   }
 }
 
-// One block of 256 threads per 16 output values: out [slot] = the sum of the blocks' slots.  16 threads per value each
-// sum a fixed stride of blocks, then the 16 in a fixed order.
+// One block of 256 threads per 16 output values: out [slot] = the sum of the blocks' slots.
 __global__ __launch_bounds__(256) void label_reduce_kernel(const double* __restrict__ ws, int nblk, int slot,
                                                            double* __restrict__ out) {
   __shared__ double red[16][16];
-  const int el = threadIdx.x & 15, part = threadIdx.x >> 4;
-  const int idx = blockIdx.x * 16 + el;
+  const int idx = blockIdx.x * 16 + (threadIdx.x & 15);
   const bool ok = idx < slot;
-  double s = 0.0;
-  if (ok)
-    for (int b = part; b < nblk; b += 16) s += ws[(int64_t)b * slot + idx];
-  red[part][el] = s;
-  __syncthreads();
-  if (part != 0 || !ok) return;
-  double t = 0.0;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) t += red[q][el];
-  out[idx] = t;
+  const double t = sum_blocks(red, nblk, ok, [&](int b) { return ws[(int64_t)b * slot + idx]; });
+  if (threadIdx.x < 16 && ok) out[idx] = t;
 }
 
-struct SelPlan {
+struct SelPlan : RowSplit {
   bool native;
-  int nblk, per_cu, pitch, slot;
-  int64_t rows_per_block;
+  int per_cu, pitch, slot;
   size_t dyn;  // dynamic LDS bytes
 };
 
@@ -302,13 +275,7 @@ SelPlan sel_plan(int64_t n, int d, int mode, int C, int K) {
   pl.slot = slot_doubles(mode, C);
   pl.per_cu = (int)(kCuLds / (static_lds(mode) + pl.dyn));
   if (pl.per_cu > 4) pl.per_cu = 4;
-  int64_t nb = (n + 1023) / 1024;
-  if (nb > (int64_t)pl.per_cu * 256) nb = (int64_t)pl.per_cu * 256;
-  const int64_t least = (n + (((int64_t)1 << 31) - 1)) >> 31;
-  if (nb < least) nb = least;
-  const int64_t rpb = ((n + nb - 1) / nb + kRows - 1) / kRows * kRows;
-  pl.rows_per_block = rpb;
-  pl.nblk = (int)((n + rpb - 1) / rpb);  // every block has rows
+  static_cast<RowSplit&>(pl) = split_rows(n, (int64_t)pl.per_cu * 256, (n + (((int64_t)1 << 31) - 1)) >> 31);
   return pl;
 }
 
