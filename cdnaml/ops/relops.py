@@ -14,13 +14,21 @@ from ._base import _native, _ptr, _stream, upload  # noqa: F401
 
 
 # ------------------------------------------------------------ K20 / K16 (relational.hip)
-def _merge_moments(part: torch.Tensor) -> torch.Tensor:
-    """Chan merge of per-block moments [nb, d, 5] (count, mean, M2, min, max) -> [d, 5]."""
+def _inf_like(t: torch.Tensor) -> torch.Tensor:
+    return torch.full_like(t, float("inf"))
+
+
+def _merge_moments(part: torch.Tensor, shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Chan merge of per-block moments [nb, d, 5] (count, mean, M2, min, max) -> [d, 5].  With ``shift`` [d] the
+    means of ``part`` are means of x - shift (what the kernel writes) and the shift is added back once."""
     cnt, mean, m2 = part[..., 0], part[..., 1], part[..., 2]
     N = cnt.sum(0)
     w = torch.where(N > 0, cnt / N.clamp_min(1), torch.zeros_like(cnt))
     mu = torch.where(cnt > 0, mean, torch.zeros_like(mean))
     M = (w * mu).sum(0)
+    # a weighted mean lies within the block means: rounding must not move it out (a constant column keeps M2 = 0)
+    M = torch.where(N > 0, torch.maximum(torch.minimum(M, torch.where(cnt > 0, mu, -_inf_like(mu)).amax(0)),
+                                         torch.where(cnt > 0, mu, _inf_like(mu)).amin(0)), M)
     dev2 = torch.where(cnt > 0, cnt * (mu - M) ** 2, torch.zeros_like(mu))
     M2 = torch.where(cnt > 0, m2, torch.zeros_like(m2)).sum(0) + dev2.sum(0)
     has = cnt > 0
@@ -28,6 +36,8 @@ def _merge_moments(part: torch.Tensor) -> torch.Tensor:
     mn = torch.where(has, part[..., 3], inf).amin(0)
     mxs = torch.where(has, part[..., 4], -inf)
     mx = torch.where(torch.isnan(mxs).any(0), torch.full_like(M, float("nan")), mxs.amax(0))
+    if shift is not None:
+        M = torch.where(N > 0, M + shift, M)
     nanmean = torch.isnan(torch.where(has, mean, torch.zeros_like(mean))).any(0)
     M = torch.where(nanmean, torch.full_like(M, float("nan")), M)
     return torch.stack([N, M, M2, mn, mx], 1)
@@ -56,7 +66,12 @@ def col_moments(X: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.
         _lib.check(_lib.lib().cdna_col_moments(0 if Xc.dtype == torch.float32 else 1, _ptr(Xc), n, d, Xc.stride(0),
                                                _ptr(v), 0 if v is None else v.stride(0), rpb, _ptr(part),
                                                _stream(X.device)), "cdna_col_moments")
-        return _merge_moments(part)
+        # the kernel ran Welford on x - shift and its partial means are means of the shifted values.  The shift is
+        # relational.hip col_moments_kernel's rule, repeated here: a column's first value, 0 if that is null or not
+        # finite.  (An outlier first value costs accuracy: in [1e16, 1, 1, ...] the 1s vanish, as in sum / count.)
+        x0 = Xc[0].double()
+        use = torch.isfinite(x0) if v is None else torch.isfinite(x0) & (v[0] != 0)
+        return _merge_moments(part, torch.where(use, x0, torch.zeros_like(x0)))
     x = X.double()
     ok = torch.ones_like(x, dtype=torch.bool) if valid is None else valid.bool()
     cnt = ok.sum(0).double()
@@ -65,7 +80,8 @@ def col_moments(X: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.
     m2 = torch.where(ok, (x - mean) ** 2, torch.zeros_like(x)).sum(0)
     mn = torch.where(ok & ~torch.isnan(x), x, torch.full_like(x, float("inf"))).amin(0)
     mx = torch.where(ok, x, torch.full_like(x, float("-inf")))
-    mx = torch.where((torch.isnan(mx)).any(0), torch.full_like(mean, float("nan")), mx.nan_to_num(float("-inf")).amax(0))
+    mx = torch.where((torch.isnan(mx)).any(0), torch.full_like(mean, float("nan")),
+                     torch.where(torch.isnan(mx), torch.full_like(mx, float("-inf")), mx).amax(0))  # inf stays inf
     return torch.stack([cnt, mean, m2, mn, mx], 1)
 
 

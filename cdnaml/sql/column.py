@@ -219,7 +219,10 @@ class BinOp(Expr):
         elif op == "%":
             zero = c == 0
             cc = torch.where(zero, torch.ones_like(c), c)
-            out = torch.fmod(a, cc)
+            if a.is_floating_point() and a.device.type == "cpu":
+                out = torch.from_numpy(np.fmod(a.numpy(), cc.numpy()))   # torch's CPU fmod: NaN for tiny divisors
+            else:
+                out = torch.fmod(a, cc)
             if bool(zero.any()):
                 valid = ~zero if valid is None else valid & ~zero
         elif op == "&":
@@ -229,7 +232,11 @@ class BinOp(Expr):
         elif op == "^":
             out = a ^ c
         elif op == "**":
-            out = torch.pow(a.double(), c.double())
+            a, c = a.double(), c.double()
+            out = torch.pow(a, c)
+            # Java Math.pow: pow(1, NaN) and pow(+-1, +-inf) are NaN where C99 (and torch) say 1
+            java_nan = torch.isnan(c) | ((a.abs() == 1) & torch.isinf(c))
+            out = torch.where(java_nan, torch.full_like(out, float("nan")), out)
             res_t = T.DoubleType()
         else:
             raise AnalysisException(f"unknown operator {op}")
@@ -279,6 +286,20 @@ class Unary(Expr):
 
 
 # ------------------------------------------------------------------ casts
+_TWO63 = 9223372036854775808.0
+
+
+def _to_integral(v: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """Java d2i / d2l of floating values: truncate, saturate at the limits of int (long for int64), NaN -> 0;
+    narrower targets then keep the low bits of the int, as Java's d2i + i2s does.  Clamped in fp64 before the
+    conversion (an out-of-range conversion is whatever the device does); 2^63 is no int64, so it is compared."""
+    v = torch.trunc(torch.nan_to_num(v.to(torch.float64), nan=0.0, posinf=float("inf"), neginf=float("-inf")))
+    if dtype == torch.int64:
+        r = v.clamp(-_TWO63, _TWO63 - 1024.0).to(torch.int64)     # 2^63 - 1024: the largest double below 2^63
+        return torch.where(v >= _TWO63, torch.full_like(r, torch.iinfo(torch.int64).max), r)
+    return v.clamp(-2147483648.0, 2147483647.0).to(torch.int32).to(dtype)
+
+
 def _cast(c: ColumnData, dt: T.DataType) -> ColumnData:
     src = c.dtype
     if src == dt:
@@ -330,7 +351,7 @@ def _cast(c: ColumnData, dt: T.DataType) -> ColumnData:
     if isinstance(dt, T.IntegralType) and c.values.dtype.is_floating_point:
         v = c.values
         bad = torch.isnan(v) | torch.isinf(v)
-        vals = torch.trunc(torch.where(bad, torch.zeros_like(v), v)).to(dt.torch_dtype)
+        vals = _to_integral(torch.where(bad, torch.zeros_like(v), v), dt.torch_dtype)
         valid = c.valid
         if bool(bad.any()):
             valid = ~bad if valid is None else valid & ~bad

@@ -17,7 +17,7 @@ from ..ops import kernels as K
 from . import types as T
 from .batch import ColumnData, column_from_numpy, full_column, map_dictionary, unify_dictionaries
 from .column import (AnalysisException, BinOp, CaseWhen, Cast, ColRef, Column, Expr, Func, IsIn, IsNaN, IsNull, Lit,
-                     RowFunc, SortOrder, Star, Unary, _cast, _to_expr)
+                     RowFunc, SortOrder, Star, Unary, _cast, _to_expr, _to_integral)
 
 
 # --------------------------------------------------------------- basics
@@ -108,7 +108,7 @@ cbrt = _math("cbrt", lambda v: torch.sign(v) * torch.abs(v) ** (1.0 / 3))
 sin = _math("sin", torch.sin)
 cos = _math("cos", torch.cos)
 tan = _math("tan", torch.tan)
-signum = _math("signum", torch.sign)
+signum = _math("signum", lambda v: torch.where((v == 0) | torch.isnan(v), v, torch.sign(v)))  # -0.0 and NaN stay
 
 
 def log(arg1, arg2=None) -> Column:
@@ -153,14 +153,25 @@ def pow(a, b) -> Column:  # noqa: A001
                         _to_expr(b if not isinstance(b, str) else col(b))))
 
 
+def _round_half_up(v: torch.Tensor, scale: int) -> torch.Tensor:
+    """HALF_UP like Spark, as expr.hip OP_ROUND computes it: t = |v| * 10^scale (one rounding; a division when the
+    scale is negative), f = floor(t) plus one where t - f >= 0.5 (floor(t + 0.5) rounds the sum up first:
+    0.49999999999999994 became 1), and v itself where t has no fraction bits (t >= 2^52, overflow, inf, NaN)."""
+    q = 10.0 ** (-scale if scale < 0 else scale)
+    t = torch.abs(v) / q if scale < 0 else torch.abs(v) * q
+    f = torch.floor(t)
+    f = f + (t - f >= 0.5).to(v.dtype)
+    r = f * q if scale < 0 else f / q
+    r = torch.where(v < 0, 0.0 - r, r)                # no negative zero, as a BigDecimal has none
+    return torch.where(t < 4503599627370496.0, r, v)
+
+
 def round(c, scale: int = 0) -> Column:  # noqa: A001
     def ev(b, ctx, args):
         a = args[0]
         if isinstance(a.dtype, T.IntegralType) and scale >= 0:
             return a
-        v = a.values.to(torch.float64)
-        m = 10.0 ** scale
-        r = torch.sign(v) * torch.floor(torch.abs(v) * m + 0.5) / m  # HALF_UP like Spark
+        r = _round_half_up(a.values.to(torch.float64), scale)
         return ColumnData(r, T.DoubleType() if not isinstance(a.dtype, T.FloatType) else T.FloatType(), a.valid)
     f = Func("round", ev, [_ce(c)], display=f"round({_ce(c).name()}, {scale})")
     f.fuse = ("round", int(scale))
@@ -178,7 +189,7 @@ def bround(c, scale: int = 0) -> Column:
 def floor(c) -> Column:
     def ev(b, ctx, args):
         a = args[0]
-        return ColumnData(torch.floor(a.values.to(torch.float64)).to(torch.int64), T.LongType(), a.valid)
+        return ColumnData(_to_integral(torch.floor(a.values.to(torch.float64)), torch.int64), T.LongType(), a.valid)
     f = Func("FLOOR", ev, [_ce(c)])
     f.fuse = "floor"
     return Column(f)
@@ -187,7 +198,7 @@ def floor(c) -> Column:
 def ceil(c) -> Column:
     def ev(b, ctx, args):
         a = args[0]
-        return ColumnData(torch.ceil(a.values.to(torch.float64)).to(torch.int64), T.LongType(), a.valid)
+        return ColumnData(_to_integral(torch.ceil(a.values.to(torch.float64)), torch.int64), T.LongType(), a.valid)
     f = Func("CEIL", ev, [_ce(c)])
     f.fuse = "ceil"
     return Column(f)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import types as T
-from .column import (Alias, BinOp, Cast, CaseWhen, ColRef, ColumnData, Expr, Func, IsNaN, IsNull, Lit, Unary)
+from .column import (_TWO63, Alias, BinOp, Cast, CaseWhen, ColRef, ColumnData, Expr, Func, IsNaN, IsNull, Lit, Unary)
 
 FUSE = os.environ.get("CDNAML_FUSE", "1") != "0"
 FUSE_MIN_ROWS = int(os.environ.get("CDNAML_FUSE_MIN_ROWS", "4096"))
@@ -33,7 +33,8 @@ FUSE_MIN_ROWS = int(os.environ.get("CDNAML_FUSE_MIN_ROWS", "4096"))
 OP = dict(LOAD=1, CONST=2, NULL=3, ADD=10, SUB=11, MUL=12, DIV=13, MOD=14, POW=15, EQ=20, NE=21, LT=22, LE=23,
           GT=24, GE=25, EQNS=26, AND=30, OR=31, NOT=39, BAND=33, BOR=34, BXOR=35, NEG=40, ABS=41, LN=42, LOG10=43,
           LOG2=44, LOG1P=45, EXP=46, EXPM1=47, SQRT=48, FLOOR=49, CEIL=50, SIGNUM=51, SIN=52, COS=53, TAN=54,
-          ROUND=55, TO_I32=60, TO_I64=61, TO_BOOL=62, TO_F32=63, ISNULL=70, ISNOTNULL=71, ISNAN=72, CASE=80)
+          ROUND=55, TO_I32=60, TO_I64=61, TO_BOOL=62, TO_F32=63, WRAP_I32=64, ISNULL=70, ISNOTNULL=71, ISNAN=72,
+          CASE=80)
 _BIN = {"+": "ADD", "-": "SUB", "*": "MUL", "/": "DIV", "%": "MOD", "**": "POW", "==": "EQ", "!=": "NE",
         "<": "LT", "<=": "LE", ">": "GT", ">=": "GE", "<=>": "EQNS", "and": "AND", "or": "OR"}
 _MATH = {"ln": "LN", "log10": "LOG10", "log2": "LOG2", "log1p": "LOG1P", "exp": "EXP", "expm1": "EXPM1",
@@ -165,6 +166,8 @@ def _compile(e: Expr, b, p: _Prog) -> T.DataType:
             if not _is(t, T.DoubleType, T.FloatType, T.IntegerType):
                 raise _Unfusable("neg type")
             p.emit("NEG", pops=1)
+            if _is(t, T.IntegerType):
+                p.emit("WRAP_I32", pops=1)      # -INT_MIN is INT_MIN
             return t
         raise _Unfusable(e.op)
     if isinstance(e, Cast):
@@ -187,6 +190,8 @@ def _compile(e: Expr, b, p: _Prog) -> T.DataType:
             if _is(t, T.DoubleType, T.FloatType):
                 p.nullable = True
                 p.emit("TO_I32" if _is(dt, T.IntegerType) else "TO_I64", pops=1)
+            elif _is(t, T.LongType) and _is(dt, T.IntegerType):
+                p.emit("WRAP_I32", pops=1)      # Java l2i keeps the low 32 bits
             return dt
         raise _Unfusable("cast target")
     if isinstance(e, IsNull):
@@ -239,8 +244,8 @@ def _compile(e: Expr, b, p: _Prog) -> T.DataType:
         if not _is(t, *_NUM_IN):
             raise _Unfusable("function arg")
         name, extra = tag if isinstance(tag, tuple) else (tag, None)
-        if isinstance(t, _LongIn) and name in ("abs", "round"):
-            raise _Unfusable("long abs/round")
+        if isinstance(t, _LongIn) and name in ("abs", "round") or _is(t, T.LongType) and name == "abs":
+            raise _Unfusable("long abs/round")     # abs(Long.MIN) is Long.MIN: not on an fp64 stack
         if name in _MATH:
             if name in ("ln", "log10", "log2", "log1p", "sqrt"):
                 p.nullable = True
@@ -250,6 +255,8 @@ def _compile(e: Expr, b, p: _Prog) -> T.DataType:
             if _is(t, T.BooleanType):
                 raise _Unfusable("abs bool")
             p.emit("ABS", pops=1)
+            if _is(t, T.IntegerType):
+                p.emit("WRAP_I32", pops=1)      # abs(INT_MIN) is INT_MIN
             return t
         if name in ("floor", "ceil"):
             p.emit("FLOOR" if name == "floor" else "CEIL", pops=1)
@@ -348,6 +355,17 @@ def can_fuse(e: Expr, b) -> bool:
 __all__ = ["evaluate", "can_fuse", "FUSE", "FUSE_MIN_ROWS", "math"]
 
 
+def _sat(x: np.ndarray, lo: float, hi: float) -> np.ndarray:
+    """expr.hip sat_i32 / sat_i64: truncate, clamp to [-lo, hi], NaN -> 0 (2^63 stands for Long.MAX)."""
+    return np.where(np.isnan(x), 0.0, np.clip(np.trunc(x), -lo, hi)) + 0.0      # + 0.0: an integer has no -0
+
+
+def _to_i64(v: np.ndarray) -> np.ndarray:
+    """expr.hip to_i64: an integral fp64 in [-2^63, 2^63] as int64, 2^63 -> Long.MAX."""
+    v = _sat(v, _TWO63, _TWO63)
+    return np.where(v >= _TWO63, np.iinfo(np.int64).max, np.clip(v, -_TWO63, _TWO63 - 1024).astype(np.int64))
+
+
 def interpret(p: _Prog, rt: T.DataType, b) -> ColumnData:
     """Host reference of expr.hip's program semantics (numpy, fp64): the CPU tests run every compiled program
     through it and compare with the operator path, so compiler bugs surface without a GPU."""
@@ -391,6 +409,8 @@ def interpret(p: _Prog, rt: T.DataType, b) -> ColumnData:
                          "GT": np.greater, "GE": np.greater_equal}.get(op)
                     if f is not None:
                         v = f(x, y).astype(float)
+                        if op == "POW":     # Java: pow(1, NaN) and pow(+-1, +-inf) are NaN where C99 says 1
+                            v = np.where(np.isnan(y) | ((np.abs(x) == 1) & np.isinf(y)), np.nan, v)
                     else:
                         v = {"BAND": bx & by, "BOR": bx | by, "BXOR": bx != by}[op].astype(float)
                 sv[-1], sm[-1] = v, m
@@ -400,24 +420,41 @@ def interpret(p: _Prog, rt: T.DataType, b) -> ColumnData:
                 v = (x == 0).astype(float)
             elif op in ("LN", "LOG10", "LOG2", "LOG1P"):
                 v = {"LN": np.log, "LOG10": np.log10, "LOG2": np.log2, "LOG1P": np.log1p}[op](x)
-                m = m & ((x > -1) if op == "LOG1P" else (x > 0))
+                m = m & ~((x <= -1) if op == "LOG1P" else (x <= 0))      # NaN stays a valid NaN
             elif op == "SQRT":
                 v = np.sqrt(x); m = m & ~(x < 0)
             elif op == "ROUND":
-                pw = 10.0 ** (arg - 128)
-                v = np.where(x > 0, 1.0, np.where(x < 0, -1.0, x)) * np.floor(np.abs(x) * pw + 0.5) / pw
+                s = arg - 128
+                q = 10.0 ** abs(s)
+                t = np.abs(x) / q if s < 0 else np.abs(x) * q
+                f = np.floor(t)
+                f = f + (t - f >= 0.5)
+                v = f * q if s < 0 else f / q
+                v = np.where(t < 2.0 ** 52, np.where(x < 0, 0.0 - v, v), x)
             elif op in ("TO_I32", "TO_I64"):
-                bad = ~np.isfinite(x); v = np.where(bad, 0.0, np.trunc(x)); m = m & ~bad
+                bad = ~np.isfinite(x); m = m & ~bad
+                v = np.where(bad, 0.0, _sat(x, 2.0 ** 31, 2.0 ** 31 - 1) if op == "TO_I32" else _sat(x, _TWO63, _TWO63))
+            elif op in ("FLOOR", "CEIL"):
+                v = _sat((np.floor if op == "FLOOR" else np.ceil)(x), _TWO63, _TWO63)
+            elif op == "WRAP_I32":
+                v = _to_i64(x).astype(np.int32).astype(float)
             elif op == "ISNULL":
                 v = (~m).astype(float); m = np.ones(n, bool)
             elif op == "ISNOTNULL":
                 v = m.astype(float); m = np.ones(n, bool)
             else:
-                v = {"NEG": np.negative, "ABS": np.abs, "EXP": np.exp, "EXPM1": np.expm1, "FLOOR": np.floor,
-                     "CEIL": np.ceil, "SIGNUM": np.sign, "SIN": np.sin, "COS": np.cos, "TAN": np.tan,
+                v = {"NEG": np.negative, "ABS": np.abs, "EXP": np.exp, "EXPM1": np.expm1, "SIN": np.sin,
+                     "COS": np.cos, "TAN": np.tan, "SIGNUM": lambda a: np.where(a > 0, 1.0, np.where(a < 0, -1.0, a)),
                      "TO_BOOL": lambda a: (a != 0).astype(float), "TO_F32": lambda a: a.astype(np.float32),
                      "ISNAN": lambda a: np.isnan(a).astype(float)}[op](x).astype(float)
             sv[-1], sm[-1] = v, m
     out_t = _OUT_T[type(rt)]
-    vals = torch.from_numpy(sv[0]).to(out_t) if out_t != torch.bool else torch.from_numpy(sv[0] != 0)
+    if out_t == torch.bool:
+        vals = torch.from_numpy(sv[0] != 0)
+    elif out_t == torch.int64:
+        vals = torch.from_numpy(_to_i64(sv[0]))
+    elif out_t == torch.int32:
+        vals = torch.from_numpy(_sat(sv[0], 2.0 ** 31, 2.0 ** 31 - 1).astype(np.int32))
+    else:
+        vals = torch.from_numpy(sv[0]).to(out_t)
     return ColumnData(vals, rt, torch.from_numpy(sm[0]) if p.nullable else None)

@@ -30,7 +30,7 @@ enum : int {
   OP_NEG = 40, OP_ABS = 41, OP_LN = 42, OP_LOG10 = 43, OP_LOG2 = 44, OP_LOG1P = 45, OP_EXP = 46,
   OP_EXPM1 = 47, OP_SQRT = 48, OP_FLOOR = 49, OP_CEIL = 50, OP_SIGNUM = 51, OP_SIN = 52, OP_COS = 53,
   OP_TAN = 54, OP_ROUND = 55,
-  OP_TO_I32 = 60, OP_TO_I64 = 61, OP_TO_BOOL = 62, OP_TO_F32 = 63,
+  OP_TO_I32 = 60, OP_TO_I64 = 61, OP_TO_BOOL = 62, OP_TO_F32 = 63, OP_WRAP_I32 = 64,
   OP_ISNULL = 70, OP_ISNOTNULL = 71, OP_ISNAN = 72,
   OP_CASE = 80,  // stack: ... acc_value, cond, branch_value -> acc (takes the branch where cond is true)
 };
@@ -56,6 +56,19 @@ __device__ __forceinline__ double load_in(const ExprArgs& a, int k, int64_t r) {
     case DT_I64: return (double)reinterpret_cast<const int64_t*>(a.in[k])[r];
     default: return reinterpret_cast<const uint8_t*>(a.in[k])[r] ? 1.0 : 0.0;
   }
+}
+
+// Java d2i / d2l on the fp64 stack: truncate, saturate at the type's limits, NaN -> 0.  Long.MAX is not a double:
+// 2^63 stands for it on the stack (what long -> double gives) and the final store maps it back.
+constexpr double kTwo63 = 9223372036854775808.0;
+__device__ __forceinline__ double sat_i32(double x) {
+  return x != x ? 0.0 : fmin(fmax(trunc(x), -2147483648.0), 2147483647.0) + 0.0;  // + 0.0: an integer has no -0
+}
+__device__ __forceinline__ double sat_i64(double x) {
+  return x != x ? 0.0 : fmin(fmax(trunc(x), -kTwo63), kTwo63) + 0.0;
+}
+__device__ __forceinline__ int64_t to_i64(double v) {  // v is integral, in [-2^63, 2^63], or NaN (a null row's filler)
+  return v >= kTwo63 ? INT64_MAX : (v >= -kTwo63 ? (int64_t)v : (v < 0.0 ? INT64_MIN : 0));
 }
 
 __global__ __launch_bounds__(kExprThreads) void expr_eval_kernel(const ExprArgs a) {
@@ -96,7 +109,9 @@ __global__ __launch_bounds__(kExprThreads) void expr_eval_kernel(const ExprArgs 
           case OP_MUL: v = x * y; break;
           case OP_DIV: v = x / (y == 0.0 ? 1.0 : y); m &= (uint8_t)(y != 0.0); break;
           case OP_MOD: v = fmod(x, y == 0.0 ? 1.0 : y); m &= (uint8_t)(y != 0.0); break;
-          case OP_POW: v = pow(x, y); break;
+          case OP_POW:  // Java Math.pow: C99's pow but for pow(1, NaN) and pow(+-1, +-inf), which are NaN, not 1
+            v = (y != y || (fabs(x) == 1.0 && isinf(y))) ? __builtin_nan("") : pow(x, y);
+            break;
           case OP_EQ: v = x == y; break;
           case OP_NE: v = x != y; break;
           case OP_LT: v = x < y; break;
@@ -142,31 +157,42 @@ __global__ __launch_bounds__(kExprThreads) void expr_eval_kernel(const ExprArgs 
         case OP_NOT: v = x == 0.0; break;
         case OP_NEG: v = -x; break;
         case OP_ABS: v = fabs(x); break;
-        case OP_LN: v = log(x); m &= (uint8_t)(x > 0.0); break;
-        case OP_LOG10: v = log10(x); m &= (uint8_t)(x > 0.0); break;
-        case OP_LOG2: v = log2(x); m &= (uint8_t)(x > 0.0); break;
-        case OP_LOG1P: v = log1p(x); m &= (uint8_t)(x > -1.0); break;
+        case OP_LN: v = log(x); m &= (uint8_t)!(x <= 0.0); break;  // null at and below the asymptote; NaN stays NaN
+        case OP_LOG10: v = log10(x); m &= (uint8_t)!(x <= 0.0); break;
+        case OP_LOG2: v = log2(x); m &= (uint8_t)!(x <= 0.0); break;
+        case OP_LOG1P: v = log1p(x); m &= (uint8_t)!(x <= -1.0); break;
         case OP_EXP: v = exp(x); break;
         case OP_EXPM1: v = expm1(x); break;
         case OP_SQRT: v = sqrt(x); m &= (uint8_t)!(x < 0.0); break;
-        case OP_FLOOR: v = floor(x); break;
-        case OP_CEIL: v = ceil(x); break;
-        case OP_SIGNUM: v = x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : (x == 0.0 ? 0.0 : x)); break;
+        case OP_FLOOR: v = sat_i64(floor(x)); break;  // to long, as Java's (long) Math.floor
+        case OP_CEIL: v = sat_i64(ceil(x)); break;
+        case OP_SIGNUM: v = x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : x); break;  // +-0 and NaN come back unchanged
         case OP_SIN: v = sin(x); break;
         case OP_COS: v = cos(x); break;
         case OP_TAN: v = tan(x); break;
-        case OP_ROUND: {  // HALF_UP at 10^arg (arg is the scale + 128)
-          const double p = pow(10.0, (double)(arg - 128));
-          v = (x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : x)) * floor(fabs(x) * p + 0.5) / p;  // torch.sign: NaN stays
+        case OP_ROUND: {  // HALF_UP at 10^-scale (arg is the scale + 128)
+          const int s = arg - 128;
+          double q = 1.0;  // 10^|scale|: exact up to 10^22, and one correctly rounded * or / by it each way
+          for (int i = 0; i < (s < 0 ? -s : s); ++i) q *= 10.0;
+          const double t = s < 0 ? fabs(x) / q : fabs(x) * q;
+          if (!(t < 4503599627370496.0)) {  // no fraction bits left (or overflow / inf / NaN): x is its own rounding
+            v = x;
+            break;
+          }
+          double f = floor(t);
+          f += (t - f >= 0.5) ? 1.0 : 0.0;  // t - f is exact; floor(t + 0.5) would round the sum up first
+          v = s < 0 ? f * q : f / q;
+          if (x < 0.0) v = 0.0 - v;  // no negative zero, as a BigDecimal has none
           break;
         }
         case OP_TO_I32:
-        case OP_TO_I64: {
+        case OP_TO_I64: {  // NaN / inf -> null, everything else saturates
           const bool bad = !isfinite(x);
-          v = bad ? 0.0 : trunc(x);
+          v = bad ? 0.0 : (op == OP_TO_I32 ? sat_i32(x) : sat_i64(x));
           m &= (uint8_t)!bad;
           break;
         }
+        case OP_WRAP_I32: v = (double)(int32_t)(uint32_t)(uint64_t)to_i64(x); break;  // Java l2i: the low 32 bits
         case OP_TO_BOOL: v = x != 0.0; break;
         case OP_TO_F32: v = (double)(float)x; break;
         case OP_ISNULL: v = !m; m = 1; break;
@@ -182,8 +208,8 @@ __global__ __launch_bounds__(kExprThreads) void expr_eval_kernel(const ExprArgs 
       switch (a.outdt) {
         case DT_F64: reinterpret_cast<double*>(a.out)[r] = v; break;
         case DT_F32: reinterpret_cast<float*>(a.out)[r] = (float)v; break;
-        case DT_I32: reinterpret_cast<int32_t*>(a.out)[r] = (int32_t)v; break;
-        case DT_I64: reinterpret_cast<int64_t*>(a.out)[r] = (int64_t)v; break;
+        case DT_I32: reinterpret_cast<int32_t*>(a.out)[r] = (int32_t)sat_i32(v); break;
+        case DT_I64: reinterpret_cast<int64_t*>(a.out)[r] = to_i64(v); break;
         default: reinterpret_cast<uint8_t*>(a.out)[r] = v != 0.0; break;
       }
       if (a.outv) a.outv[r] = sm[0][t];

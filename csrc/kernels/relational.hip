@@ -7,9 +7,10 @@
 // coalesced for the row-major layout — and each lane runs Welford in fp64 over
 // its rows.  Lanes of the same column are merged in LDS with Chan's pairwise
 // formula; per-block partials [nblk][d][5] are merged on the device the same
-// way (cdnaml/ops/kernels.py col_moments), so the result does not depend on
+// way (cdnaml/ops/relops.py _merge_moments), so the result does not depend on
 // the block schedule.  Null entries (valid == 0) are skipped, NaNs are values
-// (Spark: a NaN in a column makes its mean NaN).
+// (Spark: a NaN in a column makes its mean NaN), and an infinity gives what
+// sum / count gives: mean +-inf (NaN with both signs) and M2 NaN.
 //
 // K16 partition_by_dest: stable counting sort of rows by destination rank /
 // bucket (the all-to-all shuffle of groupBy / join / dropDuplicates /
@@ -35,6 +36,11 @@ __device__ __forceinline__ Moments merge(const Moments& a, const Moments& b) {
   r.n = a.n + b.n;
   const double delta = b.mean - a.mean;
   r.mean = a.mean + delta * (b.n / r.n);
+  // a part that saw an infinity carries mean = +-inf and M2 = NaN (NaN: a NaN or both infinities): Chan's update
+  // would turn inf + finite into NaN, so the mean follows the rule of the sum instead (M2 stays NaN by itself)
+  const bool ai = isinf(a.mean), bi = isinf(b.mean);
+  if (a.mean != a.mean || b.mean != b.mean || (ai && bi && a.mean != b.mean)) r.mean = __builtin_nan("");
+  else if (ai || bi) r.mean = ai ? a.mean : b.mean;
   r.m2 = a.m2 + b.m2 + delta * delta * (a.n * b.n / r.n);
   // Spark orders NaN above every value: min skips NaNs (fmin), max is NaN once any NaN was seen
   r.mn = fmin(a.mn, b.mn);
@@ -55,26 +61,49 @@ __global__ __launch_bounds__(kThreads) void col_moments_kernel(const TV* __restr
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
   const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
   Moments m{0.0, 0.0, 0.0, __builtin_inf(), -__builtin_inf()};
-  bool nan_seen = false;
+  // Welford runs on x - shift, the shift being the column's first value (0 if that is null or not finite), the same
+  // in every block: with a mean of 1e8 and unit spread, x - mean would carry the rounding of the mean (1.5e-8) into
+  // every delta.  The partial means are means of the shifted values; the host adds the shift back once
+  // (cdnaml/ops/relops.py col_moments computes the same shift from X[0] and valid[0]: keep the two rules in step).
+  // A first value that is an outlier by many orders of magnitude costs accuracy instead: in [1e16, 1, 1, ...] the 1s
+  // vanish in x - shift.  That is no worse than sum / count, but worse than Welford on the unshifted values.
+  const double x0 = (double)X[col];
+  const double shift = (x0 - x0 == 0.0 && (!valid || valid[col])) ? x0 : 0.0;
+  bool nan_seen = false, pinf_seen = false, ninf_seen = false;
   if (lane_r < rl) {
     for (int64_t r = r0 + lane_r; r < r1; r += rl) {
       if (valid && !valid[r * ldv + col]) continue;
       const double x = (double)X[r * ldx + col];
       if (x != x) nan_seen = true;
+      pinf_seen |= x == __builtin_inf();
+      ninf_seen |= x == -__builtin_inf();
       m.n += 1.0;
-      const double delta = x - m.mean;
+      const double xs = x - shift;
+      const double delta = xs - m.mean;
       m.mean += delta / m.n;
-      m.m2 += delta * (x - m.mean);
+      m.m2 += delta * (xs - m.mean);
       m.mn = fmin(m.mn, x);
       m.mx = fmax(m.mx, x);
     }
   }
   if (nan_seen) m.mx = __builtin_nan("");
+  if (nan_seen || pinf_seen || ninf_seen) {  // the mean of the sum: +-inf, NaN with both signs or a NaN; no M2
+    m.mean = (nan_seen || (pinf_seen && ninf_seen)) ? __builtin_nan("")
+                                                     : (pinf_seen ? __builtin_inf() : -__builtin_inf());
+    m.m2 = __builtin_nan("");
+  }
   sm[threadIdx.x] = m;
   __syncthreads();
+  // pairwise over the row lanes, in a fixed order: log2(rl) merges deep (a chain of rl = 256 merges for one column
+  // let the mean drift by several ulp)
+  int s = 1;
+  while (s < rl) s <<= 1;
+  for (s >>= 1; s > 0; s >>= 1) {
+    if (lane_r + s < rl && lane_r < s) sm[lane_r * cg + c] = merge(sm[lane_r * cg + c], sm[(lane_r + s) * cg + c]);
+    __syncthreads();
+  }
   if (lane_r == 0) {
-    Moments acc = sm[c];
-    for (int k = 1; k < rl; ++k) acc = merge(acc, sm[k * cg + c]);
+    const Moments acc = sm[c];
     double* o = part + ((int64_t)blockIdx.x * d + col) * 5;
     o[0] = acc.n;
     o[1] = acc.mean;
@@ -231,7 +260,8 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(const GatherArgs a) {
 
 CDNA_DEBUG_EXPORT(relational)
 
-// dtype: 0 = f32, 1 = f64.  part: [nblk][d][5] (count, mean, M2, min, max); nblk = ceil(n / rows_per_block).
+// dtype: 0 = f32, 1 = f64.  part: [nblk][d][5] (count, mean - shift, M2, min, max); nblk = ceil(n / rows_per_block);
+// shift = X[0][col] where that is finite and valid, else 0.
 CDNA_API int cdna_col_moments(int dtype, const void* X, int64_t n, int d, int64_t ldx, const uint8_t* valid,
                               int64_t ldv, int64_t rows_per_block, double* part, hipStream_t st) {
   if (n <= 0 || d <= 0) return 0;
