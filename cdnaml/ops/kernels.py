@@ -785,6 +785,28 @@ def hist_classes(bins: torch.Tensor, d: int, node: torch.Tensor, weight: Optiona
 
 # ------------------------------------------------------------ K5/K7 on row records
 CODE_DONE = 0xFF
+CODES_MAX_LOC = 255  # local nodes 0..254 of a tree fit the node byte next to CODE_DONE (the kernels' LDS tables)
+
+
+def _check_codes_level(tfirst: np.ndarray, A: int, tfirst_next: Optional[np.ndarray] = None,
+                       child: Optional[np.ndarray] = None) -> None:
+    """The row codes' limit: at most CODES_MAX_LOC active nodes per tree, at this level and (given the children) at
+    the next.  ValueError otherwise -- the codes kernels index 256-entry tables with the node byte."""
+    tf = np.asarray(tfirst, dtype=np.int64).reshape(-1)
+    if tf.size == 0:
+        return
+    ends = np.concatenate([tf[1:], [A]])
+    if int((ends - tf).max()) > CODES_MAX_LOC:
+        raise ValueError(f"row codes hold at most {CODES_MAX_LOC} active nodes per tree, got {int((ends - tf).max())}")
+    if child is None or A == 0:
+        return
+    ch = np.asarray(child, dtype=np.int64).reshape(-1, 2)
+    tree_of = np.searchsorted(tf, np.arange(A), side="right") - 1
+    loc = ch - np.asarray(tfirst_next, dtype=np.int64).reshape(-1)[tree_of][:, None]
+    bad = (ch >= 0) & ((loc < 0) | (loc >= CODES_MAX_LOC))
+    if bad.any():
+        raise ValueError(f"row codes hold at most {CODES_MAX_LOC} next-level nodes per tree "
+                         f"(child local index {int(loc[bad].max())})")
 
 
 def codes_init(weights: Optional[torch.Tensor], T: int, n: int, device) -> torch.Tensor:
@@ -833,7 +855,12 @@ def feature_masks(base: np.ndarray, d: int, k: int, device, base_dev: Optional[t
 
 def decode_codes(codes: torch.Tensor, tfirst: torch.Tensor):
     """codes [T, n] -> (node ids int32 [T, n] with -1 = done, weights uint8 [T, n]).  GPU: one pass
-    (seg.hip codes_to_nodes_kernel)."""
+    (seg.hip codes_to_nodes_kernel).
+
+    Besides the done codes (node byte 255) a code of weight 0 decodes to -1, on the host and in the kernel: the
+    node-id histograms and partitions that follow would carry such a row for nothing (it adds 0 to every cell, as it
+    does in the row-code histograms).  This is the histograms' reading only; ``partition_codes`` looks at the node
+    byte alone."""
     if _native(codes) and codes.dim() == 2 and codes.dtype in (torch.uint16, torch.int16):
         T, n = codes.shape
         c = codes.contiguous()
@@ -927,6 +954,14 @@ def partition_codes(bins: torch.Tensor, codes: torch.Tensor, tfirst: torch.Tenso
                     bins_fm: Optional[torch.Tensor] = None) -> None:
     """In place: every row's code moves to the chosen child's local index (255 = done).
 
+    A code is done when its NODE byte is 255, and only then: the weight byte plays no part in the move and is
+    carried untouched, so a live code whose weight byte is 0 moves like any other (``codes_init`` writes weight-0
+    rows as done from the start, and ``decode_codes`` / the histograms skip weight 0 on their own).  The host path
+    and the partition5 / partition7 kernels agree on this bit for bit.
+
+    A tree holds at most ``CODES_MAX_LOC`` active nodes at this level and at the next (the node byte; checked when
+    the tables are host tensors -- device tables come from ``split_decode`` of a forest whose depth bounds them).
+
     margin (GPU, partition5): ``(F [n] fp32, lv [3A] fp32 from split_decode, eta)`` -- rows that finish at this
     level add ``eta * leaf value`` to F (boosting margin update without a tree walk).
     bins_fm (partition5): the feature-major byte copy [G * 8, n] of ``bins`` the row bytes are gathered from."""
@@ -939,6 +974,7 @@ def partition_codes(bins: torch.Tensor, codes: torch.Tensor, tfirst: torch.Tenso
             cat_mask = torch.zeros(8, dtype=torch.int32)
         srcs = (tfirst, tfirst_next, split_feat, split_bin, cat_off, child, cat_mask)
         if all(not t.is_cuda for t in srcs):
+            _check_codes_level(tfirst.numpy(), int(split_feat.numel()), tfirst_next.numpy(), child.numpy())
             # one async host->device copy for the seven small tables (seven synchronous copies were ~0.13 ms
             # of launch gaps per level)
             args = upload(bins.device, *[t.numpy().astype(np.int32).reshape(-1) for t in srcs])
@@ -949,7 +985,9 @@ def partition_codes(bins: torch.Tensor, codes: torch.Tensor, tfirst: torch.Tenso
         # partition7 streams every bins word of every row once per level (10 GB at 1e8 x 100): it pays when
         # many trees share that pass; for few trees partition5's per-(row, tree) byte gathers move less (GBDT,
         # T = 1: 57.9 vs 40.6 ms per boosting round with partition7; CV grid with 5 / 10 trees: 2.18 vs 1.34 s)
-        if margin is None and PARTITION7 and T >= PARTITION7_MIN_T and G <= 16 and A <= 1024 and T <= 64:
+        # (its table packs a bin set's offset into 15 bits: larger mask tables take partition5 as well)
+        if margin is None and PARTITION7 and T >= PARTITION7_MIN_T and G <= 16 and A <= 1024 and T <= 64 \
+                and cat_mask.numel() <= 8 << 15:
             _lib.check(_lib.lib().cdna_partition7(
                 _ptr(bins), n, G, T, A, _ptr(codes), _ptr(args[0]), _ptr(args[1]), _ptr(args[2]), _ptr(args[3]),
                 _ptr(args[4]), _ptr(cm), _ptr(args[5]), _stream(bins.device)), "cdna_partition7")
@@ -966,14 +1004,15 @@ def partition_codes(bins: torch.Tensor, codes: torch.Tensor, tfirst: torch.Tenso
                                               _stream(bins.device)), "cdna_partition5")
         return
     assert margin is None, "margin updates run in the GPU partition only"
-    node, w = decode_codes(codes, tfirst)
-    live = node >= 0
+    _check_codes_level(tfirst.numpy(), int(split_feat.numel()), tfirst_next.numpy(), child.numpy())
+    # not decode_codes: that drops weight-0 rows (histograms), a partition moves them like any other row
+    c = codes.to(torch.int32) & 0xFFFF
+    loc = c & 0xFF
+    node = torch.where(loc == CODE_DONE, torch.full_like(loc, -1), tfirst.to(torch.int32)[:, None] + loc).contiguous()
     partition(bins, node, split_feat, split_bin, cat_off, cat_mask, child)
     tn = tfirst_next.to(torch.int32)[:, None]
     loc = torch.where(node >= 0, node - tn, torch.full_like(node, CODE_DONE))
-    loc = torch.where(live, loc, torch.full_like(loc, CODE_DONE))
-    c = (w.to(torch.int32) << 8) | loc
-    codes.copy_(c.to(torch.int16))
+    codes.copy_(((c & 0xFF00) | loc).to(torch.int16))
 
 
 # --------------------------------------------------------------------- K7
@@ -3307,6 +3346,7 @@ def codes_compact(codes: torch.Tensor, tfirst: torch.Tensor, build_slot: np.ndar
     dev = codes.device
     A = len(build_slot)
     bs = np.asarray(build_slot, dtype=np.int32)
+    _check_codes_level(tfirst.cpu().numpy(), A)
     if not _native(codes):
         c = codes.to(torch.int32) & 0xFFFF
         loc = c & 0xFF
@@ -3377,9 +3417,16 @@ def node_compact(node: torch.Tensor, w: torch.Tensor, tfirst: np.ndarray, build_
     A = len(build_slot)
     bs = np.asarray(build_slot, dtype=np.int32)
     tf_h = np.asarray(tfirst, dtype=np.int64)
+    nloc = np.diff(np.concatenate([tf_h, [A]])) if T else np.zeros(0, np.int64)
+    max_loc = int(nloc.max()) if T else 0
+    if max_loc > NODE_COMPACT_MAX_LOC:
+        raise ValueError(f"node_compact holds at most {NODE_COMPACT_MAX_LOC} active nodes per tree, got {max_loc}")
     if not _native(node):
         slot_t = torch.from_numpy(np.concatenate([bs, [-1]]).astype(np.int64))
-        ids = torch.where(node >= 0, node.long(), torch.full_like(node, A, dtype=torch.int64)).clamp_max(A)
+        # a row of tree t counts when its id is one of tree t's nodes (the kernel's table holds only those)
+        lo = torch.from_numpy(tf_h)[:, None]
+        own = (node >= lo) & (node < lo + torch.from_numpy(nloc)[:, None])
+        ids = torch.where(own, node.long(), torch.full_like(node, A, dtype=torch.int64))
         slot = slot_t[ids]
         flat = slot.reshape(-1)
         keep = torch.nonzero(flat >= 0).flatten()
@@ -3390,8 +3437,6 @@ def node_compact(node: torch.Tensor, w: torch.Tensor, tfirst: np.ndarray, build_
         wts = w.reshape(-1)[order].to(torch.int64)
         return rec_encode(rows, wts, _quant(v1[rows], rec_scale, True)), np.stack([starts, lens], 1)
     L = _lib.lib()
-    nloc = np.diff(np.concatenate([tf_h, [A]])) if T else np.zeros(0, np.int64)
-    max_loc = int(nloc.max()) if T else 0
     tf, bs_t = upload(dev, tf_h.astype(np.int32), bs)
     v1c = v1.float().contiguous()
     cnt = torch.zeros(max(S, 1), dtype=torch.int32, device=dev)
