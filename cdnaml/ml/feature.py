@@ -6,3 +6,4 @@ from ..models.feature import (Bucketizer, Imputer, ImputerModel, IndexToString, 
 from ..models.feature import (ChiSqSelector, ChiSqSelectorModel, UnivariateFeatureSelector,  # noqa: F401
                               UnivariateFeatureSelectorModel, VarianceThresholdSelector,
                               VarianceThresholdSelectorModel)
+from ..models.feature import MaxAbsScaler, MaxAbsScalerModel, RobustScaler, RobustScalerModel  # noqa: F401

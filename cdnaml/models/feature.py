@@ -758,6 +758,140 @@ class MinMaxScalerModel(Model):
         self._lo, self._hi = tensors["lo"].numpy(), tensors["hi"].numpy()
 
 
+class RobustScaler(Estimator):
+    """Scales by the quantile range (``upper`` - ``lower``) and optionally centers by the median.  The median and
+    the two quantiles of every feature come from one call of K28 ``col_quantiles``: they are exact (which meets any
+    ``relativeError``), follow the rank rule of ``percentile_approx`` and ignore NaN; a feature without a non-NaN
+    value has a NaN median and range, and its output is NaN."""
+    _params = {
+        "lower": ("lower quantile to calculate quantile range", 0.25, TC.toFloat),
+        "upper": ("upper quantile to calculate quantile range", 0.75, TC.toFloat),
+        "withCentering": ("center data with median", False, TC.toBoolean),
+        "withScaling": ("scale to quantile range", True, TC.toBoolean),
+        "inputCol": ("input column name", NO_DEFAULT, TC.toString),
+        "outputCol": ("output column name", NO_DEFAULT, TC.toString),
+        "relativeError": ("the relative target precision of the quantiles, in [0, 1]", 0.001, TC.toFloat),
+    }
+
+    def __init__(self, lower=None, upper=None, withCentering=None, withScaling=None, inputCol=None, outputCol=None,
+                 relativeError=None):
+        super().__init__()
+        keyword_init(self, dict(lower=lower, upper=upper, withCentering=withCentering, withScaling=withScaling,
+                                inputCol=inputCol, outputCol=outputCol, relativeError=relativeError))
+
+    def _fit(self, dataset):
+        from ..ops import kernels as K
+        from .util import local_xyw
+        lower, upper, err = self.getLower(), self.getUpper(), self.getRelativeError()
+        if not 0 < lower < upper < 1:
+            raise IllegalArgumentException(f"requirement failed: 0 < lower < upper < 1, got lower = {lower}, "
+                                           f"upper = {upper}")
+        if not 0 <= err <= 1:
+            raise IllegalArgumentException(f"requirement failed: relativeError must be in [0, 1], got {err}")
+        X, _, _ = local_xyw(dataset, self.getInputCol(), keep_f64=True)
+        q = K.col_quantiles(X, [lower, 0.5, upper], dataset._session.comm)["q"].double().cpu().numpy()
+        return RobustScalerModel(median=q[1], range=q[2] - q[0])
+
+
+class RobustScalerModel(Model):
+    _params = RobustScaler._params
+
+    def __init__(self, median=None, range=None):  # noqa: A002
+        super().__init__()
+        self._median = np.asarray(median if median is not None else [], dtype=np.float64)
+        self._range = np.asarray(range if range is not None else [], dtype=np.float64)
+
+    @property
+    def median(self):
+        from .linalg import DenseVector
+        return DenseVector(self._median)
+
+    @property
+    def range(self):
+        from .linalg import DenseVector
+        return DenseVector(self._range)
+
+    def _transform(self, dataset):
+        ic, oc = self.getInputCol(), self.getOutputCol()
+        wc, ws = self.getWithCentering(), self.getWithScaling()
+        med = torch.tensor(self._median, dtype=torch.float64)
+        with np.errstate(divide="ignore"):
+            scale = torch.tensor(np.where(self._range == 0, 0.0, 1.0 / self._range), dtype=torch.float64)
+
+        def fn(b, ctx):
+            X = b.columns[ic].values
+            X = X if X.dtype == torch.float64 else X.float()   # Double vectors stay Double
+            if X.shape[0] == 0:
+                X = X.new_zeros((0, len(med)))
+            Y = X
+            if wc:
+                Y = Y - med.to(b.device, X.dtype)
+            if ws:
+                Y = Y * scale.to(b.device, X.dtype)
+            return b.with_column(oc, ColumnData(Y, T.VectorUDT(), b.columns[ic].valid, meta=b.columns[ic].meta))
+        return dataset._new(MapPlan(dataset._plan, "RobustScalerModel", fn))
+
+    def _save_state(self):
+        return {}, {"median": torch.tensor(self._median), "range": torch.tensor(self._range)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._median = tensors["median"].numpy()
+        self._range = tensors["range"].numpy()
+
+
+class MaxAbsScaler(Estimator):
+    """Scales every feature into [-1, 1] by its largest absolute value, from one K28 ``col_extrema`` pass.  NaN is
+    ignored; a feature without a non-NaN value gets maxAbs = 0 (Spark gives it NaN) and passes through unscaled."""
+    _params = {
+        "inputCol": ("input column name", NO_DEFAULT, TC.toString),
+        "outputCol": ("output column name", NO_DEFAULT, TC.toString),
+    }
+
+    def __init__(self, inputCol=None, outputCol=None):
+        super().__init__()
+        keyword_init(self, dict(inputCol=inputCol, outputCol=outputCol))
+
+    def _fit(self, dataset):
+        from ..ops import kernels as K
+        from .util import local_xyw
+        X, _, _ = local_xyw(dataset, self.getInputCol(), keep_f64=True)
+        st = K.col_extrema(X, dataset._session.comm)
+        m = torch.maximum(st["min"].double().abs(), st["max"].double().abs())
+        return MaxAbsScalerModel(maxAbs=torch.where(st["count"] > 0, m, torch.zeros_like(m)).cpu().numpy())
+
+
+class MaxAbsScalerModel(Model):
+    _params = MaxAbsScaler._params
+
+    def __init__(self, maxAbs=None):
+        super().__init__()
+        self._max_abs = np.asarray(maxAbs if maxAbs is not None else [], dtype=np.float64)
+
+    @property
+    def maxAbs(self):
+        from .linalg import DenseVector
+        return DenseVector(self._max_abs)
+
+    def _transform(self, dataset):
+        ic, oc = self.getInputCol(), self.getOutputCol()
+        div = torch.tensor(np.where(self._max_abs != 0, self._max_abs, 1.0), dtype=torch.float64)
+
+        def fn(b, ctx):
+            X = b.columns[ic].values
+            X = X if X.dtype == torch.float64 else X.float()   # Double vectors stay Double
+            if X.shape[0] == 0:
+                X = X.new_zeros((0, len(div)))
+            Y = X / div.to(b.device, X.dtype)
+            return b.with_column(oc, ColumnData(Y, T.VectorUDT(), b.columns[ic].valid, meta=b.columns[ic].meta))
+        return dataset._new(MapPlan(dataset._plan, "MaxAbsScalerModel", fn))
+
+    def _save_state(self):
+        return {}, {"maxAbs": torch.tensor(self._max_abs)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._max_abs = tensors["maxAbs"].numpy()
+
+
 class Bucketizer(Transformer):
     _params = {
         "splits": ("split points", NO_DEFAULT, TC.toListFloat),

@@ -261,6 +261,11 @@ _SIGS = {
     "cdna_label_stats_workspace": ([c_int64, c_int, c_int, c_int, c_int], c_int64),
     "cdna_label_stats": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int,
                           c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_col_quantiles_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_void_p], c_int),
+    "cdna_col_digit_hist": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+                            c_int),
+    "cdna_col_select": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p], c_int),
 }
 
 

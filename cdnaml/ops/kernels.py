@@ -2714,6 +2714,288 @@ def label_stats(X: torch.Tensor, label: torch.Tensor, mode: int, C: int = 1, K: 
     return {"sx": sx, "sxx": sxx, "sxy": sxy, "sy": sy, "syy": syy, "n": cnt, "bad": bad, "bad_label": bad_label}
 
 
+# ------------------------------------------------------------ K28 col_digit_hist / col_select (quantile_select.hip)
+COLQ_MAX_D = 128               # the kernel's range: fp32 rows with d <= 128 and at most COLQ_MAX_Q targets
+COLQ_MAX_Q = 8
+COLQ_MAX_BITS = 8              # the widest digit of a pass
+COLQ_BUDGET = 96 * 1024        # LDS bytes of a block's digit table
+_I64_MIN = -(1 << 63)
+
+
+def col_quantile_widths(d: int, Q: int) -> list:
+    """The digit widths of the passes of a native quantile call for Q targets over d columns: a pure-Python mirror
+    of the kernel's plan function, which is the source of the widths wherever the library loads
+    (:func:`col_quantiles_plan`).  B(Q') is the widest b <= 8 with Q' 2^b (d | 1) 4 <= COLQ_BUDGET; pass 0 takes B(1)
+    bits and every later pass min(B(Q), bits left)."""
+    def B(q):
+        b = COLQ_MAX_BITS
+        while b > 0 and (q << b) * (d | 1) * 4 > COLQ_BUDGET:
+            b -= 1
+        return b
+    widths, left = [B(1)], 32 - B(1)
+    while left > 0:
+        widths.append(min(B(Q), left))
+        left -= widths[-1]
+    return widths
+
+
+def _colq_native_plan(X: torch.Tensor, Q: int):
+    return _row_plan(X, "cdna_col_quantiles_plan", 40, X.shape[-1], min(int(Q), 1 << 30))
+
+
+def col_quantiles_plan(X: torch.Tensor, Q: int) -> Dict[str, object]:
+    """What :func:`col_quantiles` runs for X and Q probabilities, from the dispatch's own host function (nothing is
+    launched): ``path`` "native" or "host" and ``widths``, the digit widths of the passes; for the native path
+    ``vw`` (4: float4 row loads, 1: scalar loads), ``nblk``, ``rows_per_block``, ``lds`` (bytes per block at the
+    widest pass) and ``max_bits`` = (B(1), B(Q)), the widest digit of a FIRST and of a NEXT pass."""
+    out, _ = _colq_native_plan(X, Q)
+    if out is None:
+        return {"path": "host", "widths": [8] * (8 if X.dtype == torch.float64 else 4)}
+    return {"path": "native", "vw": int(out[1]), "nblk": int(out[2]), "rows_per_block": int(out[3]),
+            "lds": int(out[4]), "max_bits": (int(out[5]), int(out[6])),
+            "widths": [int(v) for v in out[8:8 + int(out[7])]]}
+
+
+def _colq_keys(X: torch.Tensor):
+    """(keys int64, not NaN) of fp32 / fp64 values.  The keys' signed order is numeric order (-0.0 just below +0.0,
+    +-inf at the ends): the unsigned 32-bit key u ^ (sign ? 0xFFFFFFFF : 0x80000000) of an fp32 value, held in
+    int64; for fp64 the int64 bits with the magnitude bits of negative values flipped."""
+    ok = ~torch.isnan(X)
+    if X.dtype == torch.float32:
+        u = X.contiguous().view(torch.int32).long() & 0xFFFFFFFF
+        return u ^ torch.where(u >> 31 != 0, 0xFFFFFFFF, 0x80000000), ok
+    b = X.contiguous().view(torch.int64)
+    return b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFF), ok
+
+
+def _colq_values(keys: torch.Tensor, dtype) -> torch.Tensor:
+    """The values of keys (the inverse of :func:`_colq_keys`)."""
+    if dtype == torch.float32:
+        u = keys ^ torch.where(keys >> 31 != 0, 0x80000000, 0xFFFFFFFF)
+        return torch.where(u >> 31 != 0, u - (1 << 32), u).to(torch.int32).view(torch.float32)
+    return (keys ^ ((keys >> 63) & 0x7FFFFFFFFFFFFFFF)).view(torch.float64)
+
+
+def _colq_pattern(keys: torch.Tensor, kb: int) -> torch.Tensor:
+    """The keys as kb-bit unsigned patterns whose digits the passes take (in int64; kb = 64: the sign bit flipped)."""
+    return keys if kb == 32 else keys ^ _I64_MIN
+
+
+def _colq_extrema(kmin: torch.Tensor, kmax: torch.Tensor, dtype):
+    """(min, max) values of the columns' extreme keys; NaN for a column without a value (kmin > kmax)."""
+    nan = torch.full(kmin.shape, float("nan"), dtype=dtype, device=kmin.device)
+    none = kmin > kmax
+    return torch.where(none, nan, _colq_values(kmin, dtype)), torch.where(none, nan, _colq_values(kmax, dtype))
+
+
+def _digit_hist_native(Xn: torch.Tensor, Q: int, bits: int, shift: int, prefix: Optional[torch.Tensor]):
+    """One native pass of a call for Q targets; prefix: int32 [d, Q] holding the u32 prefixes, None: FIRST."""
+    n, d = Xn.shape
+    dev = Xn.device
+    first = prefix is None
+    cells = d * (1 if first else Q) << bits
+    out = torch.empty(cells + (2 * d if first else 0), dtype=torch.int64, device=dev)   # cleared by the call itself
+    _lib.check(_lib.lib().cdna_col_digit_hist(_ptr(Xn), n, Xn.stride(0), d, Q, bits, shift, _ptr(prefix), _ptr(out),
+                                              _stream(dev)), "cdna_col_digit_hist")
+    res = {"hist": out[:cells].view(d, 1 if first else Q, 1 << bits)}
+    if first:
+        km = out[cells + d:].view(torch.int32).long() & 0xFFFFFFFF
+        res.update(nan=out[cells:cells + d], kmin=km[:d], kmax=km[d:])
+    return res
+
+
+def _digit_hist_host(X: torch.Tensor, bits: int, shift: int, prefix: Optional[torch.Tensor]):
+    """One pass in plain torch ops, LABEL_HOST_CHUNK rows at a time; prefix: int64 [d, Q] patterns, None: FIRST."""
+    n, d = X.shape
+    dev = X.device
+    kb = 64 if X.dtype == torch.float64 else 32
+    first = prefix is None
+    Q = 1 if first else prefix.shape[1]
+    nd = 1 << bits
+    i64 = dict(dtype=torch.int64, device=dev)
+    hist = torch.zeros(d * Q * nd, **i64)
+    nan = torch.zeros(d, **i64)
+    kmin = torch.full((d,), (1 << (kb - 1)) - 1 if kb == 64 else (1 << 32) - 1, **i64)
+    kmax = torch.full((d,), _I64_MIN if kb == 64 else 0, **i64)
+    cols = torch.arange(d, device=dev)[None, :]
+    for i0 in range(0, n, LABEL_HOST_CHUNK):
+        keys, ok = _colq_keys(X[i0:i0 + LABEL_HOST_CHUNK])
+        pat = _colq_pattern(keys, kb)
+        digit = (pat >> shift) & (nd - 1)
+        if first:
+            hist += torch.bincount((cols * nd + digit)[ok], minlength=d * nd)
+            nan += (~ok).sum(0)
+            kmin = torch.minimum(kmin, torch.where(ok, keys, kmin[None, :]).amin(0))
+            kmax = torch.maximum(kmax, torch.where(ok, keys, kmax[None, :]).amax(0))
+            continue
+        # shift + bits < kb here: the shift is never by the key's whole width
+        hi = (pat >> (shift + bits)) & ((1 << (kb - shift - bits)) - 1)
+        for t in range(Q):
+            hit = ok & (hi == prefix[None, :, t])
+            hist += torch.bincount(((cols * Q + t) * nd + digit)[hit], minlength=d * Q * nd)
+    res = {"hist": hist.view(d, Q, nd)}
+    if first:
+        res.update(nan=nan, kmin=kmin, kmax=kmax)
+    return res
+
+
+def col_digit_hist(X: torch.Tensor, bits: int, shift: int, prefix: Optional[torch.Tensor] = None,
+                   native: bool = True) -> Dict[str, torch.Tensor]:
+    """One pass of the radix select over the local rows of X [n, d]: the counts of the key digit
+    ``(key >> shift) & (2^bits - 1)`` per column.
+
+    FIRST (``prefix`` None; ``shift + bits`` must be the key width, 32 for fp32 and 64 for fp64): every non-NaN
+    value counts; returns ``hist`` int64 [d, 1, 2^bits], ``nan`` int64 [d] and ``kmin`` / ``kmax`` int64 [d], the
+    columns' extreme keys (for fp32 2^32 - 1 / 0 for a column without a value).
+    NEXT (``prefix`` integer [d, Q], ``shift + bits`` below the key width): a value counts for every target t with
+    ``key >> (shift + bits) == prefix[c, t]``; returns ``hist`` int64 [d, Q, 2^bits].  Targets that share a prefix
+    get identical counts.
+    The key of an fp32 value is u ^ (u >> 31 ? 0xFFFFFFFF : 0x80000000), u its bits: unsigned key order is numeric
+    order.  A NaN has no key.
+
+    fp32 X on a GPU with d <= COLQ_MAX_D, Q <= COLQ_MAX_Q and ``bits`` within the plan's ``max_bits`` runs the K28
+    kernel (LDS integer atomics, 64-bit integer atomics on the table: exact, the same bits on every call); n = 0
+    launches nothing.  Everything else, and ``native=False``, takes the host formulation: the same counts from
+    ``bincount``, LABEL_HOST_CHUNK rows at a time."""
+    if X.dim() != 2:
+        raise ValueError("col_digit_hist: X must be [n, d]")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    d = X.shape[1]
+    kb = 64 if X.dtype == torch.float64 else 32
+    bits, shift = int(bits), int(shift)
+    first = prefix is None
+    if bits < 1 or bits > COLQ_MAX_BITS or shift < 0 or (shift + bits != kb if first else shift + bits >= kb):
+        raise ValueError(f"col_digit_hist: bits = {bits}, shift = {shift} for {kb}-bit keys")
+    if not first and (prefix.dim() != 2 or prefix.shape[0] != d or prefix.shape[1] < 1):
+        raise ValueError("col_digit_hist: prefix must be [d, Q]")
+    Q = 1 if first else prefix.shape[1]
+    plan, Xn = _colq_native_plan(X, Q) if native else (None, X)
+    if plan is not None and bits <= int(plan[5 if first else 6]):
+        p32 = None
+        if not first:   # the u32 prefixes in int32 storage
+            p = prefix.to(device=X.device, dtype=torch.int64) & 0xFFFFFFFF
+            p32 = torch.where(p >> 31 != 0, p - (1 << 32), p).to(torch.int32).contiguous()
+        return _digit_hist_native(Xn, Q, bits, shift, p32)
+    if not first:
+        prefix = prefix.to(device=X.device, dtype=torch.int64)
+        prefix = prefix & 0xFFFFFFFF if kb == 32 else prefix
+    return _digit_hist_host(X, bits, shift, prefix)
+
+
+def _colq_select(hist: torch.Tensor, rank: torch.Tensor, prefix: Optional[torch.Tensor], bits: int):
+    """The select step of a pass in torch ops: hist int64 [d, Q', 2^bits], rank int64 [d, Q] -> (prefix, rank)."""
+    cum = hist.cumsum(-1)
+    lt = cum < rank[:, :, None]            # the digits before the rank's digit
+    g = lt.sum(-1)
+    below = (hist * lt).sum(-1)
+    return (g if prefix is None else (prefix << bits) | g), rank - below
+
+
+def _colq_probs(probs) -> np.ndarray:
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if p.size < 1 or not bool(np.all((p >= 0) & (p <= 1))):
+        raise ValueError(f"col_quantiles: probabilities must lie in [0, 1], got {probs}")
+    return p
+
+
+def _colq_reduce_first(st, comm):
+    if comm is not None and comm.distributed:
+        comm.all_reduce(st["hist"])
+        comm.all_reduce(st["nan"])
+        comm.all_reduce(st["kmin"], "min")
+        comm.all_reduce(st["kmax"], "max")
+
+
+def col_quantiles(X: torch.Tensor, probs, comm=None, native: bool = True) -> Dict[str, torch.Tensor]:
+    """Exact quantiles of every column of X [n, d] over the rows of all ranks, by an MSB-first radix select.
+
+    With m non-NaN values in a column, the quantile for probability q is the value of 1-based rank
+    min(max(ceil(q m), 1), m) in key order (the product in fp64; -0.0 sorts just below +0.0, +-inf are ordinary
+    values): q = 0 gives the minimum, q = 1 the maximum, m = 0 NaN.  NaN values are counted and otherwise ignored.
+    Returns ``q`` [Q, d] in X's dtype, ``count`` and ``nan`` int64 [d] (the non-NaN and the NaN values) and ``min``
+    / ``max`` [d] (NaN for a column without a value).
+
+    Every pass is one :func:`col_digit_hist` over the local rows, an all-reduce of its int64 table when ``comm`` is
+    distributed (pass 0 also reduces ``nan``, ``kmin`` and ``kmax``) and a select step that extends the targets'
+    key prefixes by one digit: the result is exact, the same on every call and at every number of ranks, and no
+    row leaves its rank.  fp32 X on a GPU with d <= COLQ_MAX_D and at most COLQ_MAX_Q probabilities runs the K28
+    kernels with the widths of :func:`col_quantiles_plan`; prefixes and ranks stay on the device and a single-GPU
+    call does not synchronise with the host.  Everything else (the CPU, fp64 rows with 64-bit keys, wider inputs,
+    ``native=False``) takes the host formulation: the same algorithm in torch ops with 8-bit digits, the same bits.
+    """
+    if X.dim() != 2:
+        raise ValueError("col_quantiles: X must be [n, d]")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    p = _colq_probs(probs)
+    n, d = X.shape
+    Q = p.size
+    dev = X.device
+    plan, Xn = _colq_native_plan(X, Q) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        widths = [int(v) for v in plan[8:8 + int(plan[7])]]
+        probs_d = upload(dev, p)[0]
+        prefix = torch.empty((d, Q), dtype=torch.int32, device=dev)     # written by the first select
+        rank = torch.empty((d, Q), dtype=torch.int64, device=dev)
+        count = torch.empty(d, dtype=torch.int64, device=dev)
+        q = torch.empty((Q, d), dtype=torch.float32, device=dev)
+        shift = 32
+        for i, b in enumerate(widths):
+            shift -= b
+            st = _digit_hist_native(Xn, Q, b, shift, None if i == 0 else prefix)
+            if i == 0:
+                first = st
+                _colq_reduce_first(st, comm)
+            elif comm is not None and comm.distributed:
+                comm.all_reduce(st["hist"])
+            _lib.check(L.cdna_col_select(_ptr(st["hist"]), d, Q, b, int(i == 0), int(shift == 0), _ptr(probs_d),
+                                         _ptr(prefix), _ptr(rank), _ptr(count), _ptr(q), _stream(dev)),
+                       "cdna_col_select")
+        lo, hi = _colq_extrema(first["kmin"], first["kmax"], torch.float32)
+        return {"q": q, "count": count, "nan": first["nan"], "min": lo, "max": hi}
+    # host formulation
+    kb = 64 if X.dtype == torch.float64 else 32
+    first = _digit_hist_host(X, 8, kb - 8, None)
+    _colq_reduce_first(first, comm)
+    count = first["hist"].sum((1, 2))
+    pt = torch.from_numpy(p).to(dev)
+    rank = torch.ceil(pt[None, :] * count.double()[:, None]).long()
+    rank = torch.minimum(rank.clamp_min(1), count[:, None])
+    prefix, rank = _colq_select(first["hist"], rank, None, 8)
+    for shift in range(kb - 16, -1, -8):
+        hist = _digit_hist_host(X, 8, shift, prefix)["hist"]
+        if comm is not None and comm.distributed:
+            comm.all_reduce(hist)
+        prefix, rank = _colq_select(hist, rank, prefix, 8)
+    keys = prefix if kb == 32 else prefix ^ _I64_MIN
+    vals = _colq_values(keys, X.dtype)
+    nanv = torch.full_like(vals, float("nan"))
+    lo, hi = _colq_extrema(first["kmin"], first["kmax"], X.dtype)
+    return {"q": torch.where(count[:, None] > 0, vals, nanv).T.contiguous(), "count": count, "nan": first["nan"],
+            "min": lo, "max": hi}
+
+
+def col_extrema(X: torch.Tensor, comm=None) -> Dict[str, torch.Tensor]:
+    """Pass 0 of :func:`col_quantiles` alone: ``min`` and ``max`` [d] of the non-NaN values of every column over
+    the rows of all ranks (NaN for a column without one), ``count`` and ``nan`` int64 [d]."""
+    if X.dim() != 2:
+        raise ValueError("col_extrema: X must be [n, d]")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    plan, Xn = _colq_native_plan(X, 1)
+    if plan is not None:
+        b = int(plan[5])
+        st = _digit_hist_native(Xn, 1, b, 32 - b, None)
+    else:
+        kb = 64 if X.dtype == torch.float64 else 32
+        st = _digit_hist_host(X, 8, kb - 8, None)
+    _colq_reduce_first(st, comm)
+    lo, hi = _colq_extrema(st["kmin"], st["kmax"], X.dtype)
+    return {"min": lo, "max": hi, "count": st["hist"].sum((1, 2)), "nan": st["nan"]}
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
