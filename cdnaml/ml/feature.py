@@ -7,3 +7,4 @@ from ..models.feature import (ChiSqSelector, ChiSqSelectorModel, UnivariateFeatu
                               UnivariateFeatureSelectorModel, VarianceThresholdSelector,
                               VarianceThresholdSelectorModel)
 from ..models.feature import MaxAbsScaler, MaxAbsScalerModel, RobustScaler, RobustScalerModel  # noqa: F401
+from ..models.feature import VectorIndexer, VectorIndexerModel  # noqa: F401

@@ -892,6 +892,121 @@ class MaxAbsScalerModel(Model):
         self._max_abs = tensors["maxAbs"].numpy()
 
 
+class VectorIndexer(Estimator):
+    """``pyspark.ml.feature.VectorIndexer``: the features of a vector column with at most ``maxCategories`` distinct
+    values become categorical and are recoded to category indices; the others stay continuous.  The distinct values
+    of every feature come from one K29 ``col_distinct`` pass (per rank; the ranks' tables are united).  -0.0 and
+    +0.0 are one value; NaN is ignored at fit (Spark would count it as a value) and is an invalid value at
+    transform."""
+    _params = {
+        "inputCol": ("input column name", NO_DEFAULT, TC.toString),
+        "outputCol": ("output column name", NO_DEFAULT, TC.toString),
+        "maxCategories": ("threshold for the number of values a categorical feature can take (>= 2)", 20, TC.toInt),
+        "handleInvalid": ("how to handle invalid data (unseen values): 'skip', 'error' or 'keep'", "error",
+                          TC.toString),
+    }
+
+    def __init__(self, maxCategories=None, inputCol=None, outputCol=None, handleInvalid=None):
+        super().__init__()
+        keyword_init(self, dict(maxCategories=maxCategories, inputCol=inputCol, outputCol=outputCol,
+                                handleInvalid=handleInvalid))
+
+    def _fit(self, dataset):
+        from ..ops import kernels as K
+        from .util import local_xyw
+        cap = self.getMaxCategories()
+        if cap < 2:
+            raise IllegalArgumentException(f"requirement failed: maxCategories must be at least 2, got {cap}")
+        X, _, _ = local_xyw(dataset, self.getInputCol(), keep_f64=True)
+        st = K.col_distinct(X, cap, dataset._session.comm)
+        return VectorIndexerModel(values=st["values"].double().cpu().numpy(), count=st["count"].cpu().numpy())
+
+
+class VectorIndexerModel(Model):
+    """The value table of every feature: ``values`` [numFeatures, maxCategories + 1] ascending and ``count``
+    (above maxCategories: a continuous feature)."""
+    _params = VectorIndexer._params
+
+    def __init__(self, values=None, count=None):
+        super().__init__()
+        self._values = np.asarray(values if values is not None else np.zeros((0, 1)), dtype=np.float64)
+        self._count = np.asarray(count if count is not None else [], dtype=np.int64)
+
+    @property
+    def numFeatures(self) -> int:
+        return int(self._values.shape[0])
+
+    def _tables(self):
+        return {"values": torch.from_numpy(self._values), "count": torch.from_numpy(self._count)}
+
+    @property
+    def categoryMaps(self) -> Dict[int, Dict[float, int]]:
+        """{feature: {value: category index}} of the categorical features: the values ascending, 0.0 first."""
+        from ..ops import kernels as K
+        t = self._tables()
+        index = K.category_index(t["values"], t["count"]).numpy()
+        cap = self._values.shape[1] - 1
+        return {c: {float(self._values[c, j]): int(index[c, j]) for j in range(m)}
+                for c, m in enumerate(self._count.tolist()) if 1 <= m <= cap}
+
+    def _out_attrs(self, col_meta, ic, keep):
+        attrs = []
+        maps = self.categoryMaps
+        for i, a in enumerate(vector_attrs(col_meta, self.numFeatures, ic)):
+            if i in maps:
+                vals = [repr(v) for v, _ in sorted(maps[i].items(), key=lambda kv: kv[1])]
+                vals += ["__unknown"] if keep else []
+                a = {"idx": i, "name": a.get("name", f"{ic}_{i}"), "type": "nominal", "vals": vals,
+                     "num_vals": len(vals)}
+                if len(vals) == 2:
+                    a = {"idx": i, "name": a["name"], "type": "binary", "vals": vals}
+            attrs.append(a)
+        return {"ml_attr": {"attrs": attrs, "num_attrs": len(attrs)}}
+
+    def _transform(self, dataset):
+        from ..ops import kernels as K
+        ic, oc = self.getInputCol(), self.getOutputCol()
+        hi = self.getHandleInvalid()
+        if hi not in K.HANDLE_INVALID:
+            raise IllegalArgumentException(f"handleInvalid must be one of {K.HANDLE_INVALID}, got {hi!r}")
+        require_vector(dataset, ic)
+        raw, nf = self._tables(), self.numFeatures
+        ready, meta = {}, []        # the tables per (device, dtype) and the output attributes: made once, not per batch
+
+        def fn(b: Batch, ctx):
+            col = b.columns[ic]
+            X = col.values
+            X = X if X.dtype == torch.float64 else X.float()   # Double vectors stay Double
+            if X.shape[0] == 0:
+                X = X.new_zeros((0, nf))
+            if X.shape[1] != nf:
+                raise IllegalArgumentException(f"requirement failed: VectorIndexerModel expected a vector of "
+                                               f"length {nf} but found length {X.shape[1]}")
+            key = (X.device, X.dtype)
+            if key not in ready:
+                ready[key] = K.recode_tables(raw, X.device, X.dtype)
+            if not meta:
+                meta.append(self._out_attrs(col.meta, ic, hi == "keep"))
+            tables = ready[key]
+            Y, bad, drop = K.col_recode(X, tables, hi)
+            if hi == "error" and bool(bad.any()):
+                f = int(torch.nonzero(bad).flatten()[0])
+                raise SparkException(f"VectorIndexer encountered invalid value on feature index {f} "
+                                     f"({int(bad[f])} values). To handle or skip invalid values, try setting "
+                                     f"VectorIndexer.handleInvalid.")
+            nb = b.with_column(oc, ColumnData(Y, T.VectorUDT(), col.valid, meta=meta[0]))
+            if drop is not None and bool(drop.any()):
+                nb = nb.filter(~drop)
+            return nb
+        return dataset._new(MapPlan(dataset._plan, f"VectorIndexerModel {ic}->{oc}", fn))
+
+    def _save_state(self):
+        return {}, {"values": torch.tensor(self._values), "count": torch.tensor(self._count)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._values, self._count = tensors["values"].numpy(), tensors["count"].numpy()
+
+
 class Bucketizer(Transformer):
     _params = {
         "splits": ("split points", NO_DEFAULT, TC.toListFloat),

@@ -266,6 +266,11 @@ _SIGS = {
                             c_int),
     "cdna_col_select": ([c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_void_p], c_int),
+    "cdna_col_distinct_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_void_p], c_int),
+    "cdna_col_distinct_workspace": ([c_int64, c_int, c_int], c_int64),
+    "cdna_col_distinct": ([c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_col_recode": ([c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                         c_int64, c_void_p, c_void_p, c_void_p], c_int),
 }
 
 

@@ -2996,6 +2996,193 @@ def col_extrema(X: torch.Tensor, comm=None) -> Dict[str, torch.Tensor]:
     return {"min": lo, "max": hi, "count": st["hist"].sum((1, 2)), "nan": st["nan"]}
 
 
+# ------------------------------------------------------------ K29 col_distinct / col_recode (distinct.hip)
+DISTINCT_MAX_D = 128           # the kernels' range: fp32 rows with d <= 128 and cap <= col_distinct_max_cap(d)
+DISTINCT_BUDGET = 96 * 1024    # LDS bytes of a block's value lists (the fit) or key and index tables (the recode)
+HANDLE_INVALID = ("error", "skip", "keep")
+
+
+def col_distinct_max_cap(d: int) -> int:
+    """The largest cap the K29 kernels take at d columns: 2 (cap + 1) (d | 1) 4 bytes within DISTINCT_BUDGET (94 at
+    d = 128, 120 at d = 100).  A pure-Python mirror of the kernel's plan function, which is the source wherever
+    the library loads (:func:`col_distinct_plan`)."""
+    return DISTINCT_BUDGET // (8 * (d | 1)) - 1
+
+
+def _distinct_native_plan(X: torch.Tensor, cap: int):
+    if X.dim() != 2 or X.shape[0] == 0 or not 1 <= X.shape[1] <= DISTINCT_MAX_D:
+        return None, X
+    return _row_plan(X, "cdna_col_distinct_plan", 8, X.shape[1], min(int(cap), 1 << 30))
+
+
+def col_distinct_plan(X: torch.Tensor, cap: int) -> Dict[str, object]:
+    """What :func:`col_distinct` and :func:`col_recode` run for X and this cap, from the dispatch's own host function
+    (nothing is launched): ``path`` "native" or "host"; for the native path ``vw`` (4: the float4 instantiation, 1:
+    scalar loads), ``nblk``, ``rows_per_block``, ``lds`` (bytes per block), ``per_cu`` (blocks per CU that the LDS
+    lets in) and ``max_cap``, the largest native cap at this width."""
+    out, _ = _distinct_native_plan(X, cap)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "vw": int(out[1]), "nblk": int(out[2]), "rows_per_block": int(out[3]),
+            "lds": int(out[4]), "per_cu": int(out[5]), "max_cap": int(out[6])}
+
+
+def _distinct_keys(X: torch.Tensor):
+    """:func:`_colq_keys` after -0.0 became +0.0: the two are one value."""
+    return _colq_keys(torch.where(X == 0, torch.zeros_like(X), X))
+
+
+def _distinct_table(keys: list, nan: torch.Tensor, cap: int, dtype, dev) -> Dict[str, torch.Tensor]:
+    """The result of :func:`col_distinct` from the columns' sorted int64 key tensors (None: more than cap)."""
+    d = len(keys)
+    vals = torch.full((d, cap + 1), float("nan"), dtype=dtype, device=dev)
+    count = torch.full((d,), cap + 1, dtype=torch.int64, device=dev)
+    for c, k in enumerate(keys):
+        if k is not None:
+            vals[c, :k.numel()] = _colq_values(k, dtype)
+            count[c] = k.numel()
+    return {"values": vals, "count": count, "nan": nan}
+
+
+def _distinct_columns(st: Dict[str, torch.Tensor]) -> list:
+    """The inverse of :func:`_distinct_table`: the columns' sorted keys, None for an overflowed column."""
+    cap = st["values"].shape[1] - 1
+    return [None if m > cap else _colq_keys(st["values"][c, :m])[0] for c, m in enumerate(st["count"].tolist())]
+
+
+def col_distinct(X: torch.Tensor, cap: int, comm=None, native: bool = True) -> Dict[str, torch.Tensor]:
+    """The distinct values of every column of X [n, d] over the rows of all ranks, as far as there are at most
+    ``cap`` of them.
+
+    Returns ``values`` [d, cap + 1] in X's dtype, ``count`` int64 [d] and ``nan`` int64 [d].  A column with
+    count <= cap holds its distinct values ascending in ``values[c, :count]``; count = cap + 1 means "more than cap".
+    Slots from the count on, and every slot of a column with more than cap values, are NaN.  -0.0 and +0.0 are one
+    value (+0.0), +-inf are ordinary values; a NaN is counted in ``nan`` and otherwise ignored.
+
+    fp32 X on a GPU with d <= DISTINCT_MAX_D and cap <= ``col_distinct_max_cap(d)`` runs the K29 kernels: one pass
+    over the rows with per-thread sorted lists in LDS and a merge of the blocks' lists, exact and the same bits on
+    every call.  Everything else (the CPU, fp64 rows with 64-bit keys, wider inputs, larger caps, ``native=False``)
+    takes the host formulation: ``torch.unique`` on the keys of every column.  With a distributed ``comm`` the ranks
+    all-gather these tables and every rank takes the union under the same cap: no row leaves its rank."""
+    if X.dim() != 2:
+        raise ValueError("col_distinct: X must be [n, d]")
+    cap = int(cap)
+    if cap < 1:
+        raise ValueError(f"col_distinct: cap must be at least 1, got {cap}")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    n, d = X.shape
+    dev = X.device
+    plan, Xn = _distinct_native_plan(X, cap) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        ws = torch.empty(int(L.cdna_col_distinct_workspace(n, d, cap)), dtype=torch.int32, device=dev)
+        out = torch.empty(2 * d + (d * (cap + 1) + 1) // 2, dtype=torch.int64, device=dev)
+        _lib.check(L.cdna_col_distinct(_ptr(Xn), n, Xn.stride(0), d, cap, _ptr(ws), _ptr(out), _stream(dev)),
+                   "cdna_col_distinct")
+        count = out[:d]
+        keys = (out[2 * d:].view(torch.int32)[:d * (cap + 1)].long() & 0xFFFFFFFF).view(d, cap + 1)
+        live = torch.arange(cap + 1, device=dev)[None, :] < torch.where(count > cap, 0, count)[:, None]
+        vals = torch.where(live, _colq_values(keys, torch.float32), float("nan"))
+        st = {"values": vals, "count": count.clone(), "nan": out[d:2 * d].clone()}
+    else:
+        cols, nan = [], torch.zeros(d, dtype=torch.int64, device=dev)
+        for c in range(d):      # a column at a time: the int64 keys of the whole matrix are never held
+            keys, ok = _distinct_keys(X[:, c])
+            u = torch.unique(keys[ok])
+            cols.append(u if u.numel() <= cap else None)
+            nan[c] = n - ok.sum()
+        st = _distinct_table(cols, nan, cap, X.dtype, dev)
+    if comm is None or not comm.distributed:
+        return st
+    parts = comm.all_gather_object({k: v.cpu() for k, v in st.items()})
+    cols = [_distinct_columns(p) for p in parts]
+    merged = []
+    for c in range(d):
+        ks = [pc[c] for pc in cols]
+        u = None if any(k is None for k in ks) else torch.unique(torch.cat(ks))
+        merged.append(u if u is not None and u.numel() <= cap else None)
+    out = _distinct_table(merged, sum(p["nan"] for p in parts), cap, X.dtype, torch.device("cpu"))
+    return {k: v.to(dev) for k, v in out.items()}
+
+
+def category_index(values: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+    """int64 [d, W]: the category index of each sorted position of the value table of :func:`col_distinct` -- the
+    values ascending, except that 0.0, when present, takes index 0 and the values below it move up by one."""
+    W = values.shape[1]
+    pos = torch.arange(W, device=values.device)[None, :].expand(values.shape)
+    zero = (values == 0) & (pos < count[:, None])
+    z = torch.where(zero.any(1), zero.long().argmax(1), -1)[:, None]
+    return torch.where(pos == z, 0, torch.where(pos < z, pos + 1, pos))
+
+
+def recode_tables(tables: Dict[str, torch.Tensor], dev, dtype) -> Dict[str, object]:
+    """The tables of :func:`col_recode` made ready for X on ``dev`` in ``dtype``, once for many calls: ``values``,
+    ``ncat`` (0: a continuous column), ``index`` (:func:`category_index`), ``sizes`` (ncat as a list) and ``native``,
+    the int32 device tables of the kernel (u32 keys in int32 storage, indices, ncat)."""
+    values = tables["values"].to(device=dev, dtype=dtype)
+    count = tables["count"].to(dev)
+    ncat = torch.where(count > values.shape[1] - 1, 0, count)
+    index = category_index(values, ncat)
+    tk = _colq_keys(values.float())[0]
+    tk = torch.where(tk >> 31 != 0, tk - (1 << 32), tk).to(torch.int32).contiguous()
+    return {"values": values, "ncat": ncat, "index": index, "sizes": ncat.tolist(),
+            "native": (tk, index.to(torch.int32).contiguous(), ncat.to(torch.int32).contiguous())}
+
+
+def col_recode(X: torch.Tensor, tables: Dict[str, torch.Tensor], handle_invalid: str = "error", native: bool = True):
+    """The columns of X [n, d] that ``tables`` (the result of :func:`col_distinct`: ``values`` [d, cap + 1] and
+    ``count`` [d], or what :func:`recode_tables` made of it for X's device and dtype) holds at most cap values of,
+    recoded to their category indices (:func:`category_index`); the other columns, and those with count = 0, pass
+    through bit for bit.  Returns ``(Y, bad, drop)``: Y [n, d] in X's
+    dtype, ``bad`` int64 [d], the values of every categorical column that are not in its table (NaN included), and
+    ``drop``.  Such a value passes through under ``"error"`` (the caller raises on ``bad``), sets its row's entry
+    of the bool mask ``drop`` [n] under ``"skip"`` (None otherwise) and becomes the number of categories under
+    ``"keep"``.
+
+    The native range and the dispatch are those of :func:`col_distinct` (K29 ``col_recode_kernel``: the key and
+    index tables in LDS, one binary search per value); the host formulation is ``searchsorted`` on the keys."""
+    if handle_invalid not in HANDLE_INVALID:
+        raise ValueError(f"col_recode: handle_invalid must be one of {HANDLE_INVALID}, got {handle_invalid!r}")
+    if X.dim() != 2 or tables["values"].shape[0] != X.shape[1]:
+        raise ValueError("col_recode: X must be [n, d] and the tables must have d rows")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    n, d = X.shape
+    dev = X.device
+    mode = HANDLE_INVALID.index(handle_invalid)
+    t = tables if "ncat" in tables else recode_tables(tables, dev, X.dtype)
+    values, index, cap = t["values"], t["index"], t["values"].shape[1] - 1
+    plan, Xn = _distinct_native_plan(X, cap) if native and cap >= 1 else (None, X)
+    if plan is not None:
+        Y = torch.empty((n, d), dtype=torch.float32, device=dev)
+        wbad = torch.empty((int(plan[2]), d), dtype=torch.int32, device=dev)
+        drop = torch.empty(n, dtype=torch.uint8, device=dev) if mode == 1 else None
+        tk, ti, nc = t["native"]
+        _lib.check(_lib.lib().cdna_col_recode(_ptr(Xn), n, Xn.stride(0), d, cap, _ptr(tk), _ptr(ti), _ptr(nc), mode,
+                                              _ptr(Y), d, _ptr(wbad), _ptr(drop), _stream(dev)), "cdna_col_recode")
+        return Y, wbad.long().sum(0), (drop.bool() if drop is not None else None)
+    Y = X.clone()
+    bad = torch.zeros(d, dtype=torch.int64, device=dev)
+    drop = torch.zeros(n, dtype=torch.bool, device=dev) if mode == 1 else None
+    for c, m in enumerate(t["sizes"]):
+        if m == 0 or n == 0:
+            continue
+        keys, ok = _distinct_keys(X[:, c])
+        tk = _colq_keys(values[c, :m])[0]
+        pos = torch.searchsorted(tk, keys).clamp_max(m - 1)
+        hit = ok & (tk[pos] == keys)
+        y = index[c, pos].to(X.dtype)
+        if mode == 2:
+            Y[:, c] = torch.where(hit, y, torch.full_like(y, m))
+        else:
+            Y[:, c] = torch.where(hit, y, X[:, c])
+            if mode == 1:
+                drop |= ~hit
+        bad[c] = (~hit).sum()
+    return Y, bad, drop
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
