@@ -45,7 +45,7 @@ class KMeans(Estimator):
         super().__init__()
         keyword_init(self, kwargs)
 
-    def _init_centres(self, session, X, k, seed):
+    def _init_centres(self, session, X, k, seed, normalise=False):
         comm = session.comm
         n = X.shape[0]
         ng = global_count(session, n)
@@ -57,6 +57,8 @@ class KMeans(Estimator):
         if comm.distributed:
             samp = torch.cat(comm.all_gather_varlen(samp.contiguous()))
         S = samp.double().cpu().numpy()
+        if normalise:   # the cosine measure on rows that were not normalised beforehand (the K30 route)
+            S = S / np.maximum(np.linalg.norm(S, axis=1, keepdims=True), 1e-30)
         rng = np.random.default_rng(seed)
         if len(S) == 0:
             return np.zeros((k, X.shape[1]))
@@ -77,26 +79,39 @@ class KMeans(Estimator):
 
     def _fit(self, dataset):
         fc = self.getFeaturesCol()
-        X, _, w = local_xyw(dataset, fc, None, self.getWeightCol(), keep_f64=True)
+        X, _, w = local_xyw(dataset, fc, None, self.getWeightCol() or None, keep_f64=True)
         session = dataset._session
         comm = session.comm
         seed = self.getSeed() if self.getSeed() is not None else _default_seed(type(self))
         k = self.getK()
+        d = X.shape[1]
         cosine = self.getDistanceMeasure() == "cosine"
-        if cosine:
+        # K30 cluster_step: fp32 rows on a GPU inside its range, and (its host formulation) every weighted fit;
+        # everything else keeps K10 kmeans_step on rows normalised beforehand for the cosine measure
+        k30 = w is not None or _takes_k30(X, k, cosine)
+        if cosine and not k30:
             X = X / torch.linalg.vector_norm(X, dim=1, keepdim=True).clamp_min(1e-30)
-        C = self._init_centres(session, X, k, seed)
-        cost = float("nan")
+        C = self._init_centres(session, X, k, seed, normalise=cosine and k30)
+        # the kernel works on x - shift: the fp32 mean of the initial centres, fixed for the fit
+        shift = None if cosine else C.mean(0).astype(np.float32)
+
+        def step(C, sums=True):
+            """(assign, centre sums, weight sums, cost) of the local rows at the centres C"""
+            if k30:
+                out = K.cluster_step(X, C, K.CLUSTER_STEP if sums else K.CLUSTER_PREDICT, w, cosine, shift)
+                return (out[0], out[1], out[2], out[3]) if sums else (out[0], None, None, out[1])
+            a, S, N, c = K.kmeans_step(X, torch.tensor(C, dtype=X.dtype, device=X.device))
+            return a, S, N, c * 0.5 if cosine else c    # |x^ - c^|^2 = 2 (1 - cos)
+
         it = 0
         for it in range(self.getMaxIter()):
-            Ct = torch.tensor(C, dtype=X.dtype, device=X.device)
-            _, sums, counts, c = K.kmeans_step(X, Ct)
+            _, sums, counts, c = step(C)
             acc = torch.cat([sums.reshape(-1), counts, c.reshape(1)])
             comm.all_reduce(acc)
             a = acc.cpu().numpy()
-            S = a[: k * X.shape[1]].reshape(k, -1)
-            N = a[k * X.shape[1]: k * X.shape[1] + k]
-            newC = np.where(N[:, None] > 0, S / np.maximum(N, 1)[:, None], C)
+            S = a[: k * d].reshape(k, -1)
+            N = a[k * d: k * d + k]
+            newC = np.where(N[:, None] > 0, S / np.where(N > 0, N, 1.0)[:, None], C)
             if cosine:
                 newC = newC / np.maximum(np.linalg.norm(newC, axis=1, keepdims=True), 1e-30)
             moved = np.sqrt(((newC - C) ** 2).sum(1)).max()
@@ -104,9 +119,10 @@ class KMeans(Estimator):
             if moved <= self.getTol():
                 it += 1
                 break
-        # final cost / sizes with the final centres
-        Ct = torch.tensor(C, dtype=X.dtype, device=X.device)
-        assign, _, counts, c = K.kmeans_step(X, Ct)
+        # final cost / sizes with the final centres: the sizes are row counts, whatever the weights
+        assign, _, counts, c = step(C, sums=not k30)
+        if k30:
+            counts = torch.bincount(assign.long(), minlength=k).double()
         acc = torch.cat([counts, c.reshape(1)])
         comm.all_reduce(acc)
         a = acc.cpu().numpy()
@@ -115,6 +131,27 @@ class KMeans(Estimator):
         model.summary = KMeansSummary(model, dataset, a[:k].astype(np.int64).tolist(), float(a[k]),
                                       self.getMaxIter() if self.getMaxIter() == 0 else it)
         return model
+
+
+def _takes_k30(X, k, cosine):
+    """fp32 rows on a GPU inside K30's range.  That includes the unweighted Euclidean case K10 serves in HIP as well:
+    at 1e7 x 100 K30's step takes 3.9 ms against K10's 108 ms (profiles/r22/cluster.md)."""
+    return K.cluster_plan(X, k)["path"] == "native"
+
+
+def _assign_cost(X, C, cosine):
+    """(assign, cost) of the rows X at the centres C (numpy [k, d]), Spark's cost: sum of |x - c|^2 or 1 - cos."""
+    if X.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int32, device=X.device), torch.zeros((), dtype=torch.float64,
+                                                                               device=X.device)
+    if _takes_k30(X, C.shape[0], cosine):
+        shift = None if cosine else C.mean(0).astype(np.float32)
+        a, c, _ = K.cluster_step(X, C, K.CLUSTER_PREDICT, None, cosine, shift)
+        return a, c
+    if cosine:
+        X = X / torch.linalg.vector_norm(X, dim=1, keepdim=True).clamp_min(1e-30)
+    a, _, _, c = K.kmeans_step(X, torch.tensor(C, dtype=X.dtype, device=X.device), with_sums=False)
+    return a, c * 0.5 if cosine else c
 
 
 class KMeansSummary:
@@ -158,7 +195,7 @@ class KMeansModel(Model):
 
     def computeCost(self, dataset):
         X, _, _ = local_xyw(dataset, self.getFeaturesCol(), keep_f64=True)
-        _, _, _, c = K.kmeans_step(X, torch.tensor(self._C, dtype=X.dtype, device=X.device), with_sums=False)
+        _, c = _assign_cost(X, self._C, self.getDistanceMeasure() == "cosine")
         t = torch.tensor([float(c)], dtype=torch.float64, device=dataset._session.comm.device)
         dataset._session.comm.all_reduce(t)
         return float(t)
@@ -166,18 +203,12 @@ class KMeansModel(Model):
     def _transform(self, dataset):
         fc, pc = self.getFeaturesCol(), self.getPredictionCol()
         require_vector(dataset, fc)
-        Cd = torch.tensor(self._C, dtype=torch.float64)
         cosine = self.getDistanceMeasure() == "cosine"
 
         def fn(b, ctx):
             X = b.columns[fc].values
             X = X if X.dtype == torch.float64 else X.float()   # Double vectors: fp64 distances (kernel <double>)
-            if cosine:
-                X = X / torch.linalg.vector_norm(X, dim=1, keepdim=True).clamp_min(1e-30)
-            if X.shape[0] == 0:
-                a = torch.zeros(0, dtype=torch.int32, device=X.device)
-            else:
-                a, _, _, _ = K.kmeans_step(X, Cd.to(X.device, X.dtype), with_sums=False)
+            a, _ = _assign_cost(X, self._C, cosine)
             return b.with_column(pc, ColumnData(a.to(torch.int32), T.IntegerType()))
         return dataset._new(MapPlan(dataset._plan, "KMeansModel", fn))
 

@@ -29,6 +29,8 @@ DEBUG = os.environ.get("CDNAML_HIP_DEBUG", "0") not in ("", "0")
 LIB_PATH = os.path.join(_OUT_DIR, "libcdnaml_hip_debug.so" if DEBUG else "libcdnaml_hip.so")
 ARCH = os.environ.get("CDNAML_OFFLOAD_ARCH", "gfx950")
 _DEBUG_UNITS = ("seg", "hist5", "trees", "hashagg", "relational")
+# extra compiler flags of single translation units; cluster.hip: no packed fp32 arithmetic in its fp32 epilogues
+_UNIT_FLAGS = {"cluster.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 _lock = threading.Lock()
 _lib = None
@@ -66,7 +68,7 @@ def build(force: bool = False, verbose: bool = False, debug: bool = DEBUG) -> st
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
-        cmd = [hipcc] + flags + ["-c", src, "-o", obj]
+        cmd = [hipcc] + flags + _UNIT_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -250,6 +252,9 @@ _SIGS = {
                        c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "cdna_fm_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p], c_int),
     "cdna_fm_step_workspace": ([c_int64, c_int, c_int, c_int], c_int64),
+    "cdna_cluster_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p], c_int),
+    "cdna_cluster_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                           c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "cdna_fm_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_uint64, c_int64, c_double, c_uint32, c_void_p, c_void_p, c_void_p,
                       c_void_p], c_int),

@@ -3183,6 +3183,144 @@ def col_recode(X: torch.Tensor, tables: Dict[str, torch.Tensor], handle_invalid:
     return Y, bad, drop
 
 
+# ------------------------------------------------------------ K30 cluster_step (cluster.hip)
+CLUSTER_STEP, CLUSTER_PREDICT = 0, 1
+CLUSTER_MAX_D = 128            # the fused kernel's range: fp32 rows with d <= 128 and k <= 128
+CLUSTER_MAX_K = 128
+CLUSTER_BAD_Q = 2.0 ** 120     # a row whose |x - shift|^2 (cosine: |x|^2) is NaN or at least this is bad
+CLUSTER_HOST_ELEMS = 1 << 24   # fp64 entries (rows x k x d) per pass of the host formulation
+
+
+def _cluster_native_plan(X: torch.Tensor, k: int, mode: int):
+    if X.dim() != 2 or X.shape[0] == 0:
+        return None, X
+    return _row_plan(X, "cdna_cluster_plan", 12, X.shape[1], min(int(k), 1 << 30), int(mode))
+
+
+def cluster_plan(X: torch.Tensor, k: int, mode: int = CLUSTER_STEP) -> Dict[str, object]:
+    """What :func:`cluster_step` runs for these operands, from the dispatch's own host function (nothing is
+    launched): ``path`` "native" or "host"; for the native path ``mode``, ``slots`` (32 x 32 sum tiles per wave: 1, 2
+    or 4, and 0 for PREDICT), ``vw`` (4: float4 row loads, 1: scalar loads), ``nblk``, ``rows_per_block``,
+    ``blocks_per_cu`` (of the one round of resident blocks), ``tiles``, ``lds`` (bytes per block) and ``fold_rows``
+    (rows a block accumulates in fp32 between folds into its fp64 slab)."""
+    out, _ = _cluster_native_plan(X, k, mode)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "mode": int(mode), "slots": int(out[1]) if mode == CLUSTER_STEP else 0,
+            "vw": int(out[2]), "nblk": int(out[3]), "rows_per_block": int(out[4]), "blocks_per_cu": int(out[10]),
+            "tiles": int(out[5]), "lds": int(out[6]), "fold_rows": int(out[9])}
+
+
+def cluster_step(X: torch.Tensor, centres, mode: int = CLUSTER_STEP, w: Optional[torch.Tensor] = None,
+                 cosine: bool = False, shift=None, native: bool = True):
+    """One k-means step over the local rows, or the assignment alone.
+
+    X [n, d] fp32 or fp64, ``centres`` [k, d] (finite), ``w`` [n] row weights (None: every weight 1).  The distance
+    D of a row to a centre is |x - c|^2, or 1 - cos(x, c) with ``cosine`` (rows and centres divided by
+    max(norm, 1e-30), as Spark's cosine measure).  Every row goes to its nearest centre under K10's and
+    ``torch.min``'s rules: the lowest index among equal distances, the first NaN distance wins and stays, centre 0 when
+    every distance is +inf.  A row whose |x - shift|^2 (cosine: |x|^2) is NaN or >= CLUSTER_BAD_Q -- a non-finite
+    feature, or one the fp32 products would overflow on -- is *bad*: it goes to centre 0 at distance NaN or +inf, so
+    the cost shows it, it is counted, and it adds nothing to the sums.
+
+    CLUSTER_STEP returns ``(assign int32 [n], sums fp64 [k, d], N fp64 [k], cost, bad)``: sums_j = sum of w x over the
+    rows of centre j (x normalised under ``cosine``), N_j = their sum of w, cost = sum of w D_min, bad = the count of
+    bad rows (fp64 scalars).  CLUSTER_PREDICT returns ``(assign, cost, bad)``.
+
+    fp32 X on a GPU with d <= CLUSTER_MAX_D and k <= CLUSTER_MAX_K (any n >= 1, row stride and alignment) runs the
+    K30 kernel: the cross term of D and the centre sums on the exact-fp32 MFMA, |x|^2, D, N and the cost in fp64,
+    per-block partial sums reduced in a fixed order (two calls on the same input return the same bits).  It works
+    on x - shift (``shift`` [d], rounded to fp32; distances do not depend on it, and close to the data it removes
+    the cancellation of the expanded form), rounds w to fp32 inside the centre sums and adds N_j shift back in fp64.
+    Everything else takes the host formulation: plain fp64 torch ops in the direct form sum (x - c)^2, in row chunks
+    of CLUSTER_HOST_ELEMS / (k d) rows (``native=False`` asks for it inside the range too).
+    """
+    if X.dim() != 2:
+        raise ValueError("cluster_step: X must be [n, d]")
+    if mode not in (CLUSTER_STEP, CLUSTER_PREDICT):
+        raise ValueError(f"cluster_step: mode {mode}")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    n, d = X.shape
+    dev = X.device
+    C = torch.as_tensor(centres).detach().double().cpu().numpy()
+    if C.ndim != 2 or C.shape[1] != d or C.shape[0] < 1 or not np.isfinite(C).all():
+        raise ValueError(f"cluster_step: centres must be finite [k >= 1, {d}]")
+    k = C.shape[0]
+    sh = np.zeros(d, dtype=np.float32)
+    if shift is not None and not cosine:
+        sh = torch.as_tensor(shift).detach().cpu().numpy().astype(np.float32).reshape(-1)
+        if sh.shape[0] != d or not np.isfinite(sh).all():
+            raise ValueError(f"cluster_step: shift must be finite [{d}]")
+    step = mode == CLUSTER_STEP
+    wd = None if w is None else w.to(device=dev, dtype=torch.float64).contiguous()
+    if cosine:
+        C = C / np.maximum(np.linalg.norm(C, axis=1, keepdims=True), 1e-30)
+    plan, Xn = _cluster_native_plan(X, k, mode) if native else (None, X)
+    if plan is not None:
+        ldw = int(plan[8])
+        tab = np.zeros((int(plan[7]) // ldw, ldw), dtype=np.float32)
+        gam = np.zeros(CLUSTER_MAX_K)
+        shp = np.zeros(CLUSTER_MAX_D, dtype=np.float32)
+        if cosine:
+            tab[:d, :k] = -C.T
+            gam[:k] = 1.0
+        else:
+            with np.errstate(over="ignore"):
+                ct = (C - sh.astype(np.float64)).astype(np.float32)
+                tab[:d, :k] = -2.0 * ct.T
+            gam[:k] = (ct.astype(np.float64) ** 2).sum(1)
+            shp[:d] = sh
+            if not np.isfinite(tab).all():
+                raise ValueError("cluster_step: the centres overflow fp32")
+        tab_d, gam_d, sh_d = upload(dev, tab.reshape(-1), gam, shp)
+        assign = torch.empty(n, dtype=torch.int32, device=dev)
+        # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+        out = torch.empty(k * d + k + 2 if step else 2, dtype=torch.float64, device=dev)
+        ws = torch.empty(int(plan[11]), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().cdna_cluster_step(_ptr(Xn), n, Xn.stride(0), _ptr(wd), _ptr(tab_d), _ptr(gam_d),
+                                                _ptr(sh_d), d, k, int(cosine), int(mode), _ptr(assign), _ptr(out),
+                                                _ptr(ws), _stream(dev)), "cdna_cluster_step")
+        if not step:
+            return assign, out[0], out[1]
+        sums, N = out[:k * d].view(k, d), out[k * d:k * d + k]
+        if not cosine:
+            sums = sums + N[:, None] * sh_d[:d].double()[None, :]
+        return assign, sums, N, out[k * d + k], out[k * d + k + 1]
+    # host formulation, in row chunks: no [n, k] matrix of the whole input
+    Cd = torch.from_numpy(C).to(dev)
+    shd = torch.from_numpy(sh.astype(np.float64)).to(dev)
+    sums = torch.zeros((k, d), dtype=torch.float64, device=dev)
+    N = torch.zeros(k, dtype=torch.float64, device=dev)
+    cost = torch.zeros((), dtype=torch.float64, device=dev)
+    bad = torch.zeros((), dtype=torch.float64, device=dev)
+    parts = []
+    rows = max(1, CLUSTER_HOST_ELEMS // (k * d))
+    for i0 in range(0, n, rows):
+        Xc = X[i0:i0 + rows].double()
+        q = ((Xc - shd) ** 2).sum(1)
+        if cosine:
+            Xc = Xc / q.sqrt().clamp_min(1e-30)[:, None]
+            D = 1.0 - Xc @ Cd.T
+        else:
+            D = ((Xc[:, None, :] - Cd[None, :, :]) ** 2).sum(2)
+        best, a = D.min(dim=1)
+        isbad = ~(q < CLUSTER_BAD_Q)
+        a = torch.where(isbad, torch.zeros_like(a), a)
+        best = torch.where(isbad, torch.where(q.isnan(), q, torch.full_like(q, float("inf"))), best)
+        wc = torch.ones_like(q) if wd is None else wd[i0:i0 + rows]
+        cost += (wc * best).sum()
+        bad += isbad.sum()
+        parts.append(a.int())
+        if step:
+            A = torch.zeros((Xc.shape[0], k), dtype=torch.float64, device=dev)
+            A.scatter_(1, a[:, None], torch.where(isbad, torch.zeros_like(wc), wc)[:, None])
+            sums += A.T @ torch.where(isbad[:, None], torch.zeros_like(Xc), Xc)
+            N += A.sum(0)
+    assign = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int32, device=dev)
+    return (assign, sums, N, cost, bad) if step else (assign, cost, bad)
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
