@@ -1,9 +1,10 @@
 """Classification algorithms.
 
-LogisticRegression (binomial): every L-BFGS / OWL-QN iteration is ONE pass of
-the fused K11 HIP kernel (margin, log-loss and gradient together) plus one
-RCCL all-reduce of d+2 doubles; its margins are fp64 (Spark's Double).  Multinomial uses fp64 GEMMs at course
-sizes, fp32 device GEMMs above MULTINOMIAL_F64_MAX.  Tree
+LogisticRegression: on fp32 rows with d <= 128 and at most 32 classes every L-BFGS / OWL-QN evaluation is ONE pass
+of the fused K31 kernel (margins, log-loss or softmax cross-entropy and gradient on the fp64 MFMA: Spark's Double
+at any size) plus one all-reduce, and transform is one PREDICT pass of it.  Outside that range the binomial family
+runs the fused K11 kernel (fp64 rows, d <= 512) and multinomial uses fp64 GEMMs at course sizes, fp32 device GEMMs
+above MULTINOMIAL_F64_MAX.  Tree
 classifiers (DT / RF / GBT) share the histogram engine with class-count
 statistics (gini / entropy).  MultilayerPerceptronClassifier: every L-BFGS evaluation is one pass of the fused
 K24 kernel (forward, softmax cross-entropy, backward and weight gradients on the fp32 MFMA) plus one all-reduce of
@@ -37,6 +38,29 @@ from .util import VECTOR_F64_MAX, IllegalArgumentException, centered_gram, local
 # multinomial logistic regression: fp64 logits / gradients up to this many n*d*C multiply-adds per pass (course
 # sizes; Spark's Double), the fp32 device GEMMs above
 MULTINOMIAL_F64_MAX = 4e9
+# the binomial family's evaluations on the K31 range: K31 (True) or K11.  Measured at 1e7 x 100: K31 2.84 ms, K11
+# 8.23 ms a step (profiles/r23/linear.md)
+BINOMIAL_ON_K31 = True
+
+
+def _reduce_fg(comm, n_eff, C, g, loss, bad=None):
+    """The all-reduced [gradient | loss] of one evaluation over n_eff.  Every route reduces [g | loss | bad rows], so
+    ranks meet in one collective of one length whichever route their shard took, and all of them raise together."""
+    acc = torch.cat([g, loss.reshape(1), g.new_zeros(1) if bad is None else bad.reshape(1)])
+    comm.all_reduce(acc)
+    a = acc.cpu().numpy()
+    if a[-1] > 0:
+        raise IllegalArgumentException(
+            f"LogisticRegression: {int(a[-1])} rows have a non-finite feature or weight, a label that is not an "
+            f"integer in [0, {C}), or margins so large that the row's loss overflowed (coefficients diverged).")
+    return a[:-1] / max(n_eff, 1e-300)
+
+
+def _k31_fg(X, y, w, comm, n_eff, W, b, binomial):
+    """One K31 evaluation at the coefficients ``W`` for the raw rows: the all-reduced [gradient | loss] over n_eff."""
+    loss, g, _, bad = K.linear_step(X, y, W, b, w, binomial=binomial)
+    return _reduce_fg(comm, n_eff, 2 if binomial else len(b), g, loss, bad)
+
 
 _CLS = dict(_PRED, **{
     "probabilityCol": ("Column name for predicted class conditional probabilities.", "probability", TC.toString),
@@ -117,14 +141,17 @@ class LogisticRegression(Estimator):
         p2 = np.ones(d) if std else 1.0 / (sdz * sdz)
         p1 = np.ones(d) if std else 1.0 / sdz
         if family == "binomial":
+            k31 = BINOMIAL_ON_K31 and K.linear_on_range(X, 1)
+
             def fg(theta):
                 bs = theta[:d]
                 b0 = theta[d] if fit_int else 0.0
-                wt = torch.tensor(bs / sdz, dtype=torch.float64, device=X.device)
-                g, loss = K.logistic_grad(X, y, wt, b0, w)
-                acc = torch.cat([g, loss.reshape(1)])
-                comm.all_reduce(acc)
-                a = acc.cpu().numpy() / max(n_eff, 1e-300)
+                if k31:
+                    a = _k31_fg(X, y, w, comm, n_eff, bs / sdz, [b0], True)
+                else:
+                    wt = torch.tensor(bs / sdz, dtype=torch.float64, device=X.device)
+                    g, loss = K.logistic_grad(X, y, wt, b0, w)
+                    a = _reduce_fg(comm, n_eff, 2, g, loss)
                 grad = np.zeros(d + 1)
                 grad[:d] = a[:d] / sdz + lam * (1 - alpha) * p2 * bs
                 grad[d] = a[d] if fit_int else 0.0
@@ -143,6 +170,18 @@ class LogisticRegression(Estimator):
             coef = theta[:d] / sdz
             coef[sd == 0] = 0.0
             model = LogisticRegressionModel(coef[None, :], np.array([theta[d] if fit_int else 0.0]), 2, False)
+        elif K.linear_on_range(X, C):
+            p2c = np.tile(p2, C)
+
+            def fg(theta):
+                Wm = theta[: C * d].reshape(C, d)
+                a = _k31_fg(X, y, w, comm, n_eff, Wm / sdz[None, :], theta[C * d:] if fit_int else np.zeros(C), False)
+                grad = np.zeros(C * d + C)
+                grad[: C * d] = (a[: C * d].reshape(C, d) / sdz[None, :]).reshape(-1) + \
+                    lam * (1 - alpha) * (p2c * theta[: C * d])
+                grad[C * d:] = a[C * d: C * d + C] if fit_int else 0.0
+                f = a[-1] + 0.5 * lam * (1 - alpha) * float(np.sum(p2c * theta[: C * d] ** 2))
+                return f, grad
         else:
             Yoh = torch.nn.functional.one_hot(y.long(), C).double() if y.numel() else \
                 torch.zeros((0, C), dtype=torch.float64, device=X.device)
@@ -169,14 +208,13 @@ class LogisticRegression(Estimator):
                     R = R * wv[:, None]
                 gW = ((R.T @ X.double()) if f64 else (R.float().T @ X).double()) / sd_t.double()[None, :]
                 gb = R.sum(0)
-                acc = torch.cat([gW.reshape(-1), gb, ll.sum().reshape(1)])
-                comm.all_reduce(acc)
-                a = acc.cpu().numpy() / max(n_eff, 1e-300)
+                a = _reduce_fg(comm, n_eff, C, torch.cat([gW.reshape(-1), gb]), ll.sum())
                 grad = np.zeros(C * d + C)
                 grad[: C * d] = a[: C * d] + lam * (1 - alpha) * (np.tile(p2, C) * theta[: C * d])
                 grad[C * d:] = a[C * d: C * d + C] if fit_int else 0.0
                 f = a[-1] + 0.5 * lam * (1 - alpha) * float(np.sum(np.tile(p2, C) * theta[: C * d] ** 2))
                 return f, grad
+        if family != "binomial":
             theta0 = np.zeros(C * d + C)
             l1 = np.r_[np.tile(lam * alpha * p1, C), np.zeros(C)] if lam * alpha > 0 else None
             theta, hist, iters = minimize(fg, theta0, self.getMaxIter(), self.getTol(), l1=l1)
@@ -260,7 +298,13 @@ class LogisticRegressionModel(Model):
             if X.shape[0] == 0:
                 z = torch.zeros((0, max(self._C, 2)), dtype=torch.float64, device=X.device)
                 return _append_cls_outputs(b, z, z, z[:, 0], (names[0], names[1], names[2]))
-            if not multi:
+            if K.linear_plan(X, W.shape[0] if multi else 1)["path"] == "native":
+                # K31: the margins, the probabilities and the prediction from one pass
+                raw, prob, pred = K.linear_step(X, None, W if multi else W[0], bvec if multi else bvec[:1],
+                                                mode=K.LINEAR_PREDICT, binomial=not multi, threshold=thr)
+                if thresholds:
+                    pred = _argmax_with_thresholds(prob, thresholds)
+            elif not multi:
                 m = _margins64(X, Wd[:1])[:, 0] + bd[0]
                 raw = torch.stack([-m, m], 1)
                 p1 = torch.sigmoid(m)

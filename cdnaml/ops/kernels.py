@@ -2558,6 +2558,151 @@ def aft_step(X: torch.Tensor, logt: Optional[torch.Tensor], censor: Optional[tor
     return pred, torch.outer(pred, torch.from_numpy(qf).to(dev))
 
 
+# ------------------------------------------------------------ K31 linear_step (linear.hip)
+LINEAR_STEP, LINEAR_PREDICT = 0, 1
+LINEAR_MAX_D = 128            # the fused kernel's range: fp32 rows with d <= 128
+LINEAR_MAX_K = 32             # margins per row: 1 (binomial) or the classes of the softmax
+LINEAR_HOST_CHUNK = 1 << 18   # rows per pass of the host formulation
+
+
+def _linear_native_plan(X: torch.Tensor, K: int):
+    return _row_plan(X, "cdna_linear_plan", 8, X.shape[-1], min(int(K), 1 << 30))
+
+
+def linear_plan(X: torch.Tensor, K: int) -> Dict[str, object]:
+    """What :func:`linear_step` runs for these operands and ``K`` margins per row, from the dispatch's own host
+    function (nothing is launched): ``path`` "native" or "host"; for the native path ``KB`` (16-class blocks of the
+    fp64 MFMA), ``vw`` (4: float4 row loads, 1: scalar loads), ``nblk``, ``rows_per_block``, ``lds`` (bytes per
+    block), ``slot`` (workspace doubles per block) and ``per_cu`` (resident blocks per CU)."""
+    out, _ = _linear_native_plan(X, K)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "KB": int(out[1]), "vw": int(out[2]), "nblk": int(out[3]),
+            "rows_per_block": int(out[4]), "lds": int(out[5]), "slot": int(out[6]), "per_cu": int(out[7])}
+
+
+def linear_on_range(X: torch.Tensor, K: int) -> bool:
+    """Whether rows like ``X``'s (its device, dtype and d) with ``K`` margins are on the K31 range, whatever their
+    number: the ranks of a distributed fit answer alike, also one whose shard is empty.  (Its :func:`linear_step`
+    takes the host formulation, which returns the same shapes, so every rank reduces the same buffer.)"""
+    return linear_plan(X if X.shape[0] else X.new_zeros((1, X.shape[1])), K)["path"] == "native"
+
+
+def linear_step(X: torch.Tensor, y: Optional[torch.Tensor], W, b, w: Optional[torch.Tensor] = None,
+                mode: int = LINEAR_STEP, binomial: bool = False, threshold: float = 0.5, native: bool = True):
+    """Loss and gradient sums, or the predictions, of a binomial or multinomial logistic model over the local rows.
+
+    X [n, d] fp32 or fp64, ``y`` [n] labels (STEP only), ``w`` [n] row weights or None, all arithmetic fp64.
+    Softmax: ``W`` [C, d], ``b`` [C]; per row z = W x + b, the loss term is w (logsumexp(z) - z_y) and
+    R = w (softmax(z) - onehot(y)).  ``binomial``: ``W`` [d], ``b`` a scalar, labels 0 / 1; m = x.W + b, the loss
+    term is w (log(1 + e^m) - y m) and R = w (sigmoid(m) - y).
+
+    LINEAR_STEP returns (loss, grad, wsum, bad), fp64, un-normalised local sums: ``grad`` is [R^T X ([C][d],
+    class-major) | column sums of R [C]] (binomial: [d | intercept]), ``wsum`` the sum of the weights and ``bad`` the
+    number of bad rows.  A row is bad when it has a non-finite feature or weight, a label that is not an integer in
+    [0, C) (binomial: 0 or 1), or a loss term that is not finite (the margins overflowed); a bad row adds exactly
+    nothing to the other sums.  LINEAR_PREDICT returns (raw [n, C], prob [n, C], pred [n] int32): the margins, the
+    softmax and the lowest index among the largest probabilities; binomial: [-m, m], [1 - p, p] and p > threshold.
+
+    fp32 X on a GPU with d <= LINEAR_MAX_D and at most LINEAR_MAX_K margins (any n >= 1, row stride and alignment)
+    runs the K31 kernel: one pass, both products on the fp64 MFMA, per-block partial sums reduced in a fixed order
+    (two calls on the same input return the same bits).  Everything else takes the host formulation: plain fp64
+    torch ops, LINEAR_HOST_CHUNK rows at a time (``native=False`` asks for it inside the range too).
+    """
+    if X.dim() != 2:
+        raise ValueError("linear_step: X must be [n, d]")
+    if mode not in (LINEAR_STEP, LINEAR_PREDICT):
+        raise ValueError(f"linear_step: mode {mode}")
+    n, d = X.shape
+    dev = X.device
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    Wn = np.asarray(W.detach().cpu().numpy() if isinstance(W, torch.Tensor) else W, dtype=np.float64)
+    bn = np.asarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1)
+    Wn = Wn.reshape(1, -1) if binomial else Wn
+    if Wn.ndim != 2 or Wn.shape[1] != d or bn.shape[0] != Wn.shape[0] or (not binomial and Wn.shape[0] < 2):
+        raise ValueError(f"linear_step: W {Wn.shape} and b {bn.shape} for d = {d}, binomial = {binomial}")
+    Kn = Wn.shape[0]
+    C = 2 if binomial else Kn
+    if mode == LINEAR_STEP:
+        y = y.to(device=dev, dtype=torch.float64).contiguous()
+        w = None if w is None else w.to(device=dev, dtype=torch.float64).contiguous()
+        if y.shape != (n,) or (w is not None and w.shape != (n,)):
+            raise ValueError("linear_step: y and w must be [n]")
+    plan, Xn = _linear_native_plan(X, Kn) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        NC = 16 * int(plan[1])
+        tab = np.zeros(((d + 3) // 4 * 4, NC), dtype=np.float64)
+        tab[:d, :Kn] = Wn.T
+        tab_d, b_d = upload(dev, tab.reshape(-1), bn)
+        out = ws = raw = prob = pred = None
+        if mode == LINEAR_STEP:
+            # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+            out = torch.empty(int(plan[6]), dtype=torch.float64, device=dev)
+            ws = torch.empty(int(plan[3]) * int(plan[6]), dtype=torch.float64, device=dev)
+        else:
+            raw = torch.empty((n, C), dtype=torch.float64, device=dev)
+            prob = torch.empty((n, C), dtype=torch.float64, device=dev)
+            pred = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(L.cdna_linear_step(_ptr(Xn), n, Xn.stride(0), _ptr(y), _ptr(w), _ptr(tab_d), _ptr(b_d), d, Kn,
+                                      int(binomial), float(threshold), int(mode), _ptr(out), _ptr(ws), _ptr(raw),
+                                      _ptr(prob), _ptr(pred), _stream(dev)), "cdna_linear_step")
+        if mode == LINEAR_PREDICT:
+            return raw, prob, pred
+        G = Kn * (d + 1)
+        return out[G], out[:G], out[G + 1], out[G + 2]
+    # host formulation, LINEAR_HOST_CHUNK rows at a time
+    W_t, b_t = torch.from_numpy(Wn).to(dev), torch.from_numpy(bn).to(dev)
+    gW = torch.zeros((Kn, d), dtype=torch.float64, device=dev)
+    acc = torch.zeros(Kn + 3, dtype=torch.float64, device=dev)       # [intercepts | loss | sum w | bad]
+    outs = []
+    for i0 in range(0, n, LINEAR_HOST_CHUNK):
+        Xc = X[i0:i0 + LINEAR_HOST_CHUNK].double()
+        z = Xc @ W_t.T + b_t
+        if binomial:
+            m = z[:, 0]
+            t = torch.exp(-m.abs())
+            p1 = torch.where(m >= 0, torch.ones_like(t), t) / (1.0 + t)
+            P = p1[:, None]
+        else:
+            mx = z.max(1, keepdim=True).values
+            e = torch.exp(z - mx)
+            s = e.sum(1, keepdim=True)
+            P = e / s
+        if mode == LINEAR_PREDICT:
+            if binomial:
+                outs.append((torch.stack([-m, m], 1), torch.stack([1.0 - p1, p1], 1), (p1 > threshold).int()))
+            else:
+                outs.append((z, P, _first_argmax(P)))
+            continue
+        yc = y[i0:i0 + LINEAR_HOST_CHUNK]
+        wc = torch.ones_like(yc) if w is None else w[i0:i0 + LINEAR_HOST_CHUNK]
+        lab = (yc >= 0) & (yc < C) & (yc == yc.floor())
+        yi = torch.where(lab, yc, torch.zeros_like(yc)).long()
+        if binomial:
+            loss = wc * (torch.log1p(t) + m.clamp_min(0.0) - yc * m)
+            R = (wc * (p1 - yc))[:, None]
+        else:
+            oh = torch.nn.functional.one_hot(yi, C).double()
+            loss = wc * (mx[:, 0] + torch.log(s[:, 0]) - z.gather(1, yi[:, None])[:, 0])
+            R = wc[:, None] * (P - oh)
+        ok = lab & torch.isfinite(Xc).all(1) & torch.isfinite(wc) & torch.isfinite(loss)
+        zero = torch.zeros_like(loss)
+        R = torch.where(ok[:, None], R, zero[:, None])
+        gW += R.T @ torch.where(ok[:, None], Xc, zero[:, None])      # predicated: never a NaN times zero
+        acc[:Kn] += R.sum(0)
+        acc[Kn] += torch.where(ok, loss, zero).sum()
+        acc[Kn + 1] += torch.where(ok, wc, zero).sum()
+        acc[Kn + 2] += (~ok).sum()
+    if mode == LINEAR_STEP:
+        return acc[Kn], torch.cat([gW.reshape(-1), acc[:Kn]]), acc[Kn + 1], acc[Kn + 2]
+    if not outs:
+        z0 = torch.zeros((0, C), dtype=torch.float64, device=dev)
+        return z0, z0.clone(), torch.zeros(0, dtype=torch.int32, device=dev)
+    return tuple(torch.cat(p) for p in zip(*outs))
+
+
 # ------------------------------------------------------------ K27 label_stats (select.hip)
 LABEL_COUNT, LABEL_CLASS, LABEL_REGRESS = 0, 1, 2
 LABEL_MAX_D = 128              # the fused kernel's range: fp32 rows with d <= 128
