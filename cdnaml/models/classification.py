@@ -919,7 +919,10 @@ class NaiveBayesModel(Model):
 
 
 class LinearSVC(Estimator):
-    """Linear SVM (squared hinge smoothed with L-BFGS on device GEMV passes)."""
+    """Linear SVM: the squared hinge (1 / sum w) sum w max(0, 1 - s m)^2 + lambda |beta|^2 / 2 minimised by L-BFGS.
+    Every evaluation is one pass of the K32 ``margin_step`` op over the local rows plus one all-reduce of d + 4
+    doubles [gradient | loss | sum w | bad rows]; a row with a non-finite feature or weight or a label other than
+    0 / 1 raises."""
     _params = dict(_PRED, **{
         "rawPredictionCol": ("raw prediction column name", "rawPrediction", TC.toString),
         "maxIter": ("max number of iterations", 100, TC.toInt),
@@ -939,26 +942,21 @@ class LinearSVC(Estimator):
         X, y, w = local_xyw(dataset, self.getFeaturesCol(), self.getLabelCol(), self.getWeightCol())
         comm = dataset._session.comm
         d = X.shape[1]
-        ys = (2 * y - 1)
-        ww = w if w is not None else torch.ones_like(y)
-        nt = torch.tensor([float(ww.sum())], dtype=torch.float64, device=X.device)
-        comm.all_reduce(nt)
-        n = float(nt)
         lam = self.getRegParam()
 
         def fg(theta):
-            wt = torch.tensor(theta[:d], dtype=torch.float32, device=X.device)
-            m = (X @ wt).double() + theta[d]
-            marg = 1 - ys * m
-            act = marg > 0
-            loss = (ww * torch.where(act, marg * marg, torch.zeros_like(marg))).sum()
-            r = torch.where(act, -2 * ys * marg, torch.zeros_like(marg)) * ww
-            g = torch.cat([(r.float() @ X).double(), r.sum().reshape(1), loss.reshape(1)])
-            comm.all_reduce(g)
-            a = g.cpu().numpy() / n
-            grad = a[: d + 1].copy()
+            loss, g, wsum, bad = K.margin_step(X, y, theta[:d], theta[d], w, loss=K.MARGIN_SQUARED_HINGE)
+            acc = torch.cat([g[:d + 1], loss.reshape(1), wsum.reshape(1), bad.reshape(1)])
+            comm.all_reduce(acc)
+            a = acc.cpu().numpy()
+            if a[d + 3] > 0:
+                raise IllegalArgumentException(
+                    f"LinearSVC: {int(a[d + 3])} rows have a non-finite feature or weight, a label that is not 0 or "
+                    f"1, or a margin so large that the row's loss overflowed (coefficients diverged).")
+            n = max(a[d + 2], 1e-300)
+            grad = a[: d + 1] / n
             grad[:d] += lam * theta[:d]
-            return a[d + 1] + 0.5 * lam * float(theta[:d] @ theta[:d]), grad
+            return a[d + 1] / n + 0.5 * lam * float(theta[:d] @ theta[:d]), grad
         theta, hist, it = minimize(fg, np.zeros(d + 1), self.getMaxIter(), self.getTol())
         return LinearSVCModel(theta[:d], theta[d])
 
@@ -981,12 +979,10 @@ class LinearSVCModel(Model):
 
     def _transform(self, dataset):
         fc, pc, rc = self.getFeaturesCol(), self.getPredictionCol(), self.getRawPredictionCol()
-        wt = torch.tensor(self._w, dtype=torch.float32)
         b0, thr = self._b, self.getThreshold()
 
         def fn(b, ctx):
-            X = b.columns[fc].values.float()
-            m = (X @ wt.to(X.device)).double() + b0
+            m = K.margin_step(b.columns[fc].values.float(), None, self._w, b0, mode=K.MARGIN_PREDICT)
             nb = b.with_column(rc, ColumnData(torch.stack([-m, m], 1).float(), T.VectorUDT()))
             return nb.with_column(pc, ColumnData((m > thr).double(), T.DoubleType()))
         return dataset._new(MapPlan(dataset._plan, "LinearSVCModel", fn))

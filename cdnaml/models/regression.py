@@ -209,6 +209,8 @@ class LinearRegression(Estimator):
         require_vector(dataset, fc)
         from .util import require_numeric
         require_numeric(dataset, lc)
+        if self.getLoss() == "huber":
+            return self._fit_huber(dataset, fc, lc, wc)
         src = streamed_columns(dataset, fc, [lc] + ([wc] if wc else []), head_rows=4096)
         if src is not None:
             return self._fit_streamed(dataset, src, lc, wc)
@@ -254,6 +256,67 @@ class LinearRegression(Estimator):
         preds = model.transform(dataset)
         model.summary = LinearRegressionTrainingSummary(preds, lc, self.getPredictionCol(), d, hist, iters,
                                                         stderr, coef, intercept)
+        return model
+
+    def _fit_huber(self, dataset, fc, lc, wc):
+        """``loss="huber"``: Spark's robust fit, the scale sigma estimated with the coefficients.  L-BFGS
+        (``optim.minimize``, which has no bounds: sigma goes through its logarithm) over [beta_std | intercept |
+        log sigma] from the all-zero point, so sigma starts at 1.  The objective is (1 / sum w) sum loss +
+        regParam |beta|^2 / 2 with the penalty on the standardised coefficients (``standardization``) or on the
+        original-scale ones; the label is not standardised.  Every evaluation is one pass of the K32 ``margin_step``
+        op over the local rows plus one all-reduce of d + 5 doubles."""
+        from .optim import minimize
+        from .util import centered_gram
+        eps, lam = self.getEpsilon(), self.getRegParam()
+        if self.getElasticNetParam() != 0.0:
+            raise IllegalArgumentException("requirement failed: LinearRegression with huber loss only supports L2 "
+                                           f"regularization, but got elasticNetParam = {self.getElasticNetParam()}.")
+        if self.getSolver() == "normal":
+            raise IllegalArgumentException("requirement failed: LinearRegression with huber loss doesn't support "
+                                           "normal solver, please change solver to auto or l-bfgs.")
+        if not eps > 1.0:
+            raise IllegalArgumentException(f"requirement failed: epsilon must be > 1.0, got {eps}")
+        X, y, w = local_xyw(dataset, fc, lc, wc, keep_f64=True)
+        comm = dataset._session.comm
+        d = X.shape[1]
+        n, _, Cg = centered_gram(X, comm)
+        if n <= 0:
+            raise IllegalArgumentException("requirement failed: empty training dataset")
+        sd = np.sqrt(np.clip(torch.diagonal(Cg).cpu().numpy(), 0, None) / max(n - 1, 1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = np.where(sd > 0, 1.0 / sd, 0.0)     # a zero-std feature takes no part, as in Spark
+        p2 = np.ones(d) if self.getStandardization() else inv * inv
+        fit_int = self.getFitIntercept()
+        evals = [0]
+
+        def fg(theta):
+            bs, b0, sigma = theta[:d], theta[d] if fit_int else 0.0, math.exp(theta[d + 1])
+            evals[0] += 1
+            if not 0.0 < sigma < math.inf:
+                return float("inf"), np.zeros(d + 2)
+            ls, g, wsum, bad = K.margin_step(X, y, bs * inv, b0, w, loss=K.MARGIN_HUBER, sigma=sigma, epsilon=eps)
+            acc = torch.cat([g, ls.reshape(1), wsum.reshape(1), bad.reshape(1)])
+            comm.all_reduce(acc)
+            a = acc.cpu().numpy()
+            if a[d + 4] > 0:
+                if evals[0] == 1:
+                    raise IllegalArgumentException(
+                        f"LinearRegression: {int(a[d + 4])} rows have a non-finite feature, label or weight")
+                return float("inf"), np.zeros(d + 2)     # a term overflowed: the line search shortens the step
+            nw = max(a[d + 3], 1e-300)
+            grad = a[:d + 2] / nw
+            grad[:d] = grad[:d] * inv + lam * p2 * bs
+            grad[d] = grad[d] if fit_int else 0.0
+            grad[d + 1] *= sigma                          # d / d log sigma
+            return a[d + 2] / nw + 0.5 * lam * float(np.sum(p2 * bs * bs)), grad
+
+        theta, hist, iters = minimize(fg, np.zeros(d + 2), self.getMaxIter(), self.getTol())
+        coef = theta[:d] * inv
+        intercept = float(theta[d]) if fit_int else 0.0
+        model = LinearRegressionModel(coef, intercept, math.exp(theta[d + 1]))
+        model._post_fit(self)
+        model.summary = LinearRegressionTrainingSummary(model.transform(dataset), lc, self.getPredictionCol(), d,
+                                                        hist, iters, None, coef, intercept)
         return model
 
     def _fit_streamed(self, dataset, src, lc, wc):
@@ -473,10 +536,11 @@ class LinearRegression(Estimator):
 class LinearRegressionModel(Model):
     _params = LinearRegression._params
 
-    def __init__(self, coefficients=None, intercept=0.0):
+    def __init__(self, coefficients=None, intercept=0.0, scale=1.0):
         super().__init__()
         self._coef = np.asarray(coefficients if coefficients is not None else [], dtype=np.float64)
         self._intercept = float(intercept)
+        self._scale = float(scale)
         self.summary = None
 
     @property
@@ -497,7 +561,8 @@ class LinearRegressionModel(Model):
 
     @property
     def scale(self):
-        return 1.0
+        """The Huber fit's sigma; 1.0 for ``loss="squaredError"``."""
+        return self._scale
 
     def predict(self, features):
         x = features.toArray() if hasattr(features, "toArray") else np.asarray(features)
@@ -525,11 +590,12 @@ class LinearRegressionModel(Model):
                                   self.numFeatures)
 
     def _save_state(self):
-        return {"intercept": self._intercept}, {"coefficients": torch.tensor(self._coef)}
+        return {"intercept": self._intercept, "scale": self._scale}, {"coefficients": torch.tensor(self._coef)}
 
     def _load_state(self, extra, tensors, stages):
         self._coef = tensors["coefficients"].numpy()
         self._intercept = float(extra["intercept"])
+        self._scale = float(extra.get("scale", 1.0))
         self.summary = None
 
     def __repr__(self):

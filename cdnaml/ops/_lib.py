@@ -265,6 +265,9 @@ _SIGS = {
     "cdna_linear_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_void_p], c_int),
     "cdna_linear_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                           c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_margin_plan": ([c_void_p, c_int64, c_int64, c_int, c_void_p], c_int),
+    "cdna_margin_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_int,
+                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "cdna_label_stats_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p], c_int),
     "cdna_label_stats_workspace": ([c_int64, c_int, c_int, c_int, c_int], c_int64),
     "cdna_label_stats": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int,

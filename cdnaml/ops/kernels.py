@@ -2703,6 +2703,143 @@ def linear_step(X: torch.Tensor, y: Optional[torch.Tensor], W, b, w: Optional[to
     return tuple(torch.cat(p) for p in zip(*outs))
 
 
+# ------------------------------------------------------------ K32 margin_step (margin.hip)
+MARGIN_STEP, MARGIN_PREDICT = 0, 1
+MARGIN_SQUARED_HINGE, MARGIN_HUBER = 0, 1
+MARGIN_MAX_D = 128            # the fused kernel's range: fp32 rows with d <= 128
+MARGIN_HOST_CHUNK = 1 << 18   # rows per pass of the host formulation
+
+
+def _margin_native_plan(X: torch.Tensor):
+    return _row_plan(X, "cdna_margin_plan", 7, X.shape[-1])
+
+
+def margin_plan(X: torch.Tensor) -> Dict[str, object]:
+    """What :func:`margin_step` runs for these operands, from the dispatch's own host function (nothing is
+    launched): ``path`` "native" or "host"; for the native path ``vw`` (4: float4 row loads, 1: scalar loads),
+    ``nblk``, ``rows_per_block``, ``lds`` (bytes per block), ``slot`` (workspace doubles per block) and ``per_cu``
+    (resident blocks per CU)."""
+    out, _ = _margin_native_plan(X)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "vw": int(out[1]), "nblk": int(out[2]), "rows_per_block": int(out[3]),
+            "lds": int(out[4]), "slot": int(out[5]), "per_cu": int(out[6])}
+
+
+def margin_on_range(X: torch.Tensor) -> bool:
+    """Whether rows like ``X``'s (its device, dtype and d) are on the K32 range, whatever their number: the ranks of
+    a distributed fit answer alike, also one whose shard is empty.  (Its :func:`margin_step` takes the host
+    formulation, which returns the same shapes, so every rank reduces the same buffer.)"""
+    return margin_plan(X if X.shape[0] else X.new_zeros((1, X.shape[1])))["path"] == "native"
+
+
+def margin_step(X: torch.Tensor, y: Optional[torch.Tensor], coef, intercept: float, w: Optional[torch.Tensor] = None,
+                loss: int = MARGIN_SQUARED_HINGE, mode: int = MARGIN_STEP, sigma: float = 1.0,
+                epsilon: float = 1.35, native: bool = True):
+    """Loss and gradient sums, or the margins, of a linear model with one margin per row over the local rows.
+
+    X [n, d] fp32 or fp64, ``y`` [n] labels (STEP only), ``w`` [n] row weights or None, ``coef`` [d] fp64 for the
+    rows as they are, all arithmetic fp64.  Per row m = x.coef + intercept, and ``loss`` chooses the top:
+
+    * MARGIN_SQUARED_HINGE (LinearSVC; labels 0 / 1): s = 2 y - 1, t = 1 - s m; if t > 0 the loss term is w t^2 and
+      u = -2 w s t, otherwise both are 0 (t == 0 is inactive).
+    * MARGIN_HUBER (Spark's HuberAggregator, scale ``sigma``, shape ``epsilon``): r = y - m; if |r| <= epsilon sigma
+      the loss term is w (sigma + r^2 / sigma) / 2, u = -w r / sigma, v = w (1 - (r / sigma)^2) / 2; otherwise
+      w (sigma + 2 epsilon |r| - sigma epsilon^2) / 2, u = -w epsilon sign(r), v = w (1 - epsilon^2) / 2.
+
+    MARGIN_STEP returns (loss, grad, wsum, bad), fp64, un-normalised local sums: ``grad`` [d + 2] = [sum u x | sum u
+    | sum v] (coefficients, intercept, sigma; the last is 0 for the hinge), ``wsum`` the sum of the weights and
+    ``bad`` the number of bad rows.  A row is bad when it has a non-finite feature or weight, a label that is not 0
+    or 1 (hinge) or not finite (Huber), or a loss, u or v term that is not finite; a bad row adds exactly nothing to
+    the other sums.  MARGIN_PREDICT returns the margins [n] fp64.
+
+    fp32 X on a GPU with d <= MARGIN_MAX_D (any n >= 1, row stride and alignment) runs the K32 kernel: one pass,
+    per-block partial sums reduced in a fixed order (two calls on the same input return the same bits).  Everything
+    else takes the host formulation: plain fp64 torch ops, MARGIN_HOST_CHUNK rows at a time (``native=False`` asks
+    for it inside the range too: bench/margin_micro.py times the two side by side).
+    """
+    if X.dim() != 2:
+        raise ValueError("margin_step: X must be [n, d]")
+    if mode not in (MARGIN_STEP, MARGIN_PREDICT) or loss not in (MARGIN_SQUARED_HINGE, MARGIN_HUBER):
+        raise ValueError(f"margin_step: mode {mode}, loss {loss}")
+    n, d = X.shape
+    dev = X.device
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    cf = np.asarray(coef.detach().cpu().numpy() if isinstance(coef, torch.Tensor) else coef,
+                    dtype=np.float64).reshape(-1)
+    if cf.shape[0] != d:
+        raise ValueError(f"margin_step: {cf.shape[0]} coefficients for d = {d}")
+    b0, sigma, eps = float(intercept), float(sigma), float(epsilon)
+    huber = loss == MARGIN_HUBER
+    if mode == MARGIN_STEP:
+        if huber and not (0.0 < sigma < math.inf and 0.0 < eps < math.inf):
+            raise ValueError(f"margin_step: sigma {sigma} and epsilon {eps} must be positive and finite")
+        y = y.to(device=dev, dtype=torch.float64).contiguous()
+        w = None if w is None else w.to(device=dev, dtype=torch.float64).contiguous()
+        if y.shape != (n,) or (w is not None and w.shape != (n,)):
+            raise ValueError("margin_step: y and w must be [n]")
+    plan, Xn = _margin_native_plan(X) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        cf_d = upload(dev, cf)[0]
+        out = ws = marg = None
+        if mode == MARGIN_STEP:
+            # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+            out = torch.empty(d + 5, dtype=torch.float64, device=dev)
+            ws = torch.empty(int(plan[2]) * int(plan[5]), dtype=torch.float64, device=dev)
+        else:
+            y = w = None
+            marg = torch.empty(n, dtype=torch.float64, device=dev)
+        _lib.check(L.cdna_margin_step(_ptr(Xn), n, Xn.stride(0), _ptr(y), _ptr(w), _ptr(cf_d), b0, sigma, eps, d,
+                                      int(loss), int(mode), _ptr(out), _ptr(ws), _ptr(marg), _stream(dev)),
+                   "cdna_margin_step")
+        if mode == MARGIN_PREDICT:
+            return marg
+        return out[d + 2], out[:d + 2], out[d + 3], out[d + 4]
+    # host formulation, MARGIN_HOST_CHUNK rows at a time
+    cf_t = torch.from_numpy(cf).to(dev)
+    acc = torch.zeros(d + 5, dtype=torch.float64, device=dev)
+    margs = []
+    for i0 in range(0, n, MARGIN_HOST_CHUNK):
+        Xc = X[i0:i0 + MARGIN_HOST_CHUNK].double()
+        m = Xc @ cf_t + b0
+        if mode == MARGIN_PREDICT:
+            margs.append(m)
+            continue
+        yc = y[i0:i0 + MARGIN_HOST_CHUNK]
+        wc = torch.ones_like(yc) if w is None else w[i0:i0 + MARGIN_HOST_CHUNK]
+        zero = torch.zeros_like(m)
+        if huber:
+            r = yc - m
+            q = r / sigma
+            quad = r.abs() <= eps * sigma
+            ls = 0.5 * wc * torch.where(quad, sigma + r * q, sigma + 2.0 * eps * r.abs() - sigma * eps * eps)
+            u = torch.where(quad, -wc * q, torch.where(r < 0, wc * eps, -wc * eps))
+            v = 0.5 * wc * torch.where(quad, 1.0 - q * q, torch.full_like(q, 1.0 - eps * eps))
+            lab = torch.isfinite(yc)
+        else:
+            s = 2.0 * yc - 1.0
+            t = 1.0 - s * m
+            act = ~(t <= 0)          # a NaN margin is active: its terms are NaN and the row is bad
+            ls = torch.where(act, wc * t * t, zero)
+            u = torch.where(act, -2.0 * wc * s * t, zero)
+            v = zero
+            lab = (yc == 0) | (yc == 1)
+        ok = lab & torch.isfinite(Xc).all(1) & torch.isfinite(wc) & torch.isfinite(ls) & torch.isfinite(u) & \
+            torch.isfinite(v)
+        u = torch.where(ok, u, zero)
+        acc[:d] += torch.where(ok[:, None], Xc, zero[:, None]).T @ u        # predicated: never a NaN times zero
+        acc[d] += u.sum()
+        acc[d + 1] += torch.where(ok, v, zero).sum()
+        acc[d + 2] += torch.where(ok, ls, zero).sum()
+        acc[d + 3] += torch.where(ok, wc, zero).sum()
+        acc[d + 4] += (~ok).sum()
+    if mode == MARGIN_PREDICT:
+        return torch.cat(margs) if margs else torch.zeros(0, dtype=torch.float64, device=dev)
+    return acc[d + 2], acc[:d + 2], acc[d + 3], acc[d + 4]
+
+
 # ------------------------------------------------------------ K27 label_stats (select.hip)
 LABEL_COUNT, LABEL_CLASS, LABEL_REGRESS = 0, 1, 2
 LABEL_MAX_D = 128              # the fused kernel's range: fp32 rows with d <= 128
