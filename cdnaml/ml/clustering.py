@@ -1,2 +1,3 @@
-from ..models.clustering import (BisectingKMeans, GaussianMixture, GaussianMixtureModel,  # noqa: F401
-                                 GaussianMixtureSummary, KMeans, KMeansModel, KMeansSummary, MultivariateGaussian)
+from ..models.clustering import (BisectingKMeans, BisectingKMeansModel, BisectingKMeansSummary,  # noqa: F401
+                                 GaussianMixture, GaussianMixtureModel, GaussianMixtureSummary, KMeans, KMeansModel,
+                                 KMeansSummary, MultivariateGaussian)

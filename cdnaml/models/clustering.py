@@ -221,45 +221,215 @@ class KMeansModel(Model):
 
 
 class BisectingKMeans(KMeans):
-    """Divisive k-means: repeatedly split the largest cluster with 2-means."""
+    """Spark's bisecting k-means (mllib's level-wise algorithm): a binary tree of clusters, node i with the children
+    2 i and 2 i + 1.  Every level bisects all divisible leaves together (the largest by weight when more are divisible
+    than leaves are still needed, ties to the lower index) with ``maxIter`` passes of the K33 ``bisect_step`` op --
+    every row takes one side of the bisector of its leaf's two children -- each followed by one all-reduce of the
+    children's (W, cnt, S, Q) sums, from which centre and cost of a cluster both come.  No row leaves its rank and no
+    copy of the rows is made: a row carries the split entry of its leaf in an int32."""
     _params = dict(KMeans._params, minDivisibleClusterSize=("min points in a divisible cluster", 1.0, TC.toFloat))
 
     def _fit(self, dataset):
-        fc = self.getFeaturesCol()
-        X, _, _ = local_xyw(dataset, fc, keep_f64=True)
-        session = dataset._session
-        comm = session.comm
+        X, _, w = local_xyw(dataset, self.getFeaturesCol(), None, self.getWeightCol() or None, keep_f64=True)
+        comm = dataset._session.comm
         seed = self.getSeed() if self.getSeed() is not None else _default_seed(type(self))
-        centers = [None]
-        mean = X.double().sum(0)
-        cnt = torch.tensor([float(X.shape[0])], dtype=torch.float64, device=X.device)
-        comm.all_reduce_many([mean, cnt])
-        centers = [(mean / cnt).cpu().numpy()]
+        cosine = self.getDistanceMeasure() == "cosine"
+        d = X.shape[1]
+        node = torch.zeros(X.shape[0], dtype=torch.int32, device=X.device)
+        shift = np.zeros(d, dtype=np.float32)
+
+        def step(h, t):
+            """the children's [L, 2] W and Q and [L, 2, d] S over all ranks: one all-reduce of 2 L (d + 3) doubles"""
+            L = len(t)
+            W, cnt, S, Q, bad = K.bisect_step(X, h, t, [-1] * L, [-1] * L, K.BISECT_STEP, node, w, cosine, shift)
+            acc = torch.cat([W.reshape(-1), cnt.reshape(-1), Q.reshape(-1), S.reshape(-1), bad.reshape(1)])
+            comm.all_reduce(acc)
+            a = acc.cpu().numpy()
+            if a[-1] > 0:
+                raise ValueError(f"BisectingKMeans: {int(a[-1])} rows of column {self.getFeaturesCol()} have "
+                                 f"non-finite or overflowing values")
+            return a[:2 * L].reshape(L, 2), a[6 * L:-1].reshape(L, 2, d), a[4 * L:6 * L].reshape(L, 2)
+
+        # the root: one everything-left entry; the Euclidean fit works in the frame of the fp32 global mean
+        root = (np.zeros((1, d)), [np.inf])
+        W, S, Q = step(*root)
+        if not W[0, 0] > 0:
+            raise ValueError("BisectingKMeans: the training dataset has no weight")
+        if not cosine:
+            shift = (S[0, 0] / W[0, 0]).astype(np.float32)
+            W, S, Q = step(*root)
+        info = {1: _cluster_summary(W[0, 0], S[0, 0], Q[0, 0], cosine)}
+        mds = self.getMinDivisibleClusterSize()
+        min_size = mds if mds >= 1.0 else mds * W[0, 0]
         rng = np.random.default_rng(seed)
-        while len(centers) < self.getK():
-            C = np.array(centers)
-            assign, _, counts, _ = K.kmeans_step(X, torch.tensor(C, dtype=X.dtype, device=X.device))
-            comm.all_reduce(counts)
-            big = int(torch.argmax(counts))
-            sub = X[assign.long() == big]
-            base = centers[big]
-            jitter = rng.normal(scale=1e-3, size=base.shape) * (np.abs(base) + 1)
-            pair = np.stack([base + jitter, base - jitter])
-            for _ in range(self.getMaxIter()):
-                _, s2, c2, _ = K.kmeans_step(sub, torch.tensor(pair, dtype=X.dtype, device=X.device))
-                acc = torch.cat([s2.reshape(-1), c2])
-                comm.all_reduce(acc)
-                a = acc.cpu().numpy()
-                S2, N2 = a[: 2 * X.shape[1]].reshape(2, -1), a[2 * X.shape[1]:]
-                newp = np.where(N2[:, None] > 0, S2 / np.maximum(N2, 1)[:, None], pair)
-                if np.abs(newp - pair).max() < self.getTol():
-                    pair = newp
-                    break
-                pair = newp
-            centers = centers[:big] + [pair[0], pair[1]] + centers[big + 1:]
-        model = KMeansModel(np.array(centers))
+        max_iter, need = self.getMaxIter(), self.getK() - 1
+
+        def divisible(active):
+            div = [i for i in active if info[i][0] >= min_size and info[i][2] > _BISECT_EPS * info[i][0]]
+            return sorted(sorted(div, key=lambda i: (-info[i][0], i))[:max(need, 0)])
+
+        div = divisible([1]) if max_iter > 0 else []
+        while div:
+            cen = {}
+            for i in div:            # Spark's splitCenter
+                c = info[i][1]
+                noise = rng.random(d)
+                level = 1e-4 * np.linalg.norm(c + shift.astype(np.float64))
+                for child, sign in ((2 * i, -1.0), (2 * i + 1, 1.0)):
+                    v = c + sign * level * noise
+                    cen[child] = v / max(np.linalg.norm(v), 1e-30) if cosine else v
+            for _ in range(max_iter):
+                W, S, Q = step(*_split_table(div, cen, d))
+                new = {}
+                for e, i in enumerate(div):
+                    for s in (0, 1):
+                        if 2 * i + s in cen:
+                            if W[e, s] > 0:
+                                new[2 * i + s] = _cluster_summary(W[e, s], S[e, s], Q[e, s], cosine)
+                                cen[2 * i + s] = new[2 * i + s][1]
+                            else:          # an empty child drops out for good: its sibling takes every row
+                                del cen[2 * i + s]
+            info.update(new)
+            need -= len(div)
+            nxt = divisible(sorted(new))
+            if nxt:                  # commit the level: every row moves on to its child's entry of the next level
+                h, t = _split_table(div, cen, d)
+                tg = [[nxt.index(2 * i + s) if 2 * i + s in nxt else -1 for i in div] for s in (0, 1)]
+                K.bisect_step(X, h, t, tg[0], tg[1], K.BISECT_ASSIGN, node, None, cosine, shift)
+            div = nxt
+        index = np.array(sorted(info), dtype=np.int64)
+        model = BisectingKMeansModel(index, np.array([info[i][1] for i in index]) + shift.astype(np.float64),
+                                     np.array([info[i][2] for i in index]), np.array([info[i][0] for i in index]),
+                                     shift)
         model._post_fit(self)
+        tab = model._tables()
+        leaf = model._descend(X, tab)[0]
+        sizes = torch.bincount(leaf.long(), minlength=len(tab["leaves"])).double()
+        comm.all_reduce(sizes)
+        model.summary = BisectingKMeansSummary(model, dataset, sizes.cpu().numpy().astype(np.int64).tolist(),
+                                               float(model._cost[tab["leaves"]].sum()), max_iter)
         return model
+
+
+_BISECT_EPS = 2.220446049250313e-16
+
+
+def _cluster_summary(W, S, Q, cosine):
+    """(W, centre, cost) of a cluster from its sums: the weight, the sum of w x~ and the sum of w |x~|^2 (Euclidean:
+    in the shifted frame, which the cost does not depend on)."""
+    if cosine:
+        norm = float(np.linalg.norm(S))
+        return float(W), S / max(norm, 1e-30), max(float(W) - norm, 0.0)
+    return float(W), S / W, max(float(Q) - float(S @ S) / float(W), 0.0)
+
+
+def _split_entry(cl, cr, d):
+    """(h, t) of the bisector of two centres; a missing child (None) is h = 0 and t = +-inf."""
+    if cl is None or cr is None:
+        return np.zeros(d), (-np.inf if cl is None and cr is not None else np.inf)
+    return cr - cl, (float(cr @ cr) - float(cl @ cl)) / 2.0
+
+
+def _split_table(div, cen, d):
+    rows = [_split_entry(cen.get(2 * i), cen.get(2 * i + 1), d) for i in div]
+    return np.array([r[0] for r in rows]), [r[1] for r in rows]
+
+
+class BisectingKMeansSummary(KMeansSummary):
+    """clusterSizes (row counts per predicted leaf), trainingCost (the sum of the leaves' costs), numIter (maxIter),
+    k, predictions and cluster."""
+
+
+class BisectingKMeansModel(Model):
+    """The tree of a bisecting k-means fit: ``index`` (tree indices, ascending: the children of node i are 2 i and
+    2 i + 1), per node the centre, the cost and the weight, and the fit's shift.  The leaves, numbered depth-first and
+    left first, are the clusters; prediction descends the tree (at every node to the closer child), which is not the
+    nearest leaf."""
+    _params = BisectingKMeans._params
+
+    def __init__(self, index=None, centers=None, costs=None, weights=None, shift=None):
+        super().__init__()
+        self._index = np.asarray(index if index is not None else np.zeros(0), dtype=np.int64)
+        self._C = np.asarray(centers if centers is not None else np.zeros((0, 0)), dtype=np.float64)
+        self._cost = np.asarray(costs if costs is not None else np.zeros(0), dtype=np.float64)
+        self._W = np.asarray(weights if weights is not None else np.zeros(0), dtype=np.float64)
+        self._shift = np.asarray(shift if shift is not None else np.zeros(self._C.shape[1:]), dtype=np.float32)
+        self.summary = None
+
+    def _tables(self):
+        """The PREDICT table of the tree, entries in depth-first order (targets point forward): h, t, left, right,
+        and ``leaves``: the positions in ``index`` of the leaves in cluster order."""
+        pos = {int(i): j for j, i in enumerate(self._index)}
+        cosine = self.getDistanceMeasure() == "cosine"
+        Ct = self._C if cosine else self._C - self._shift.astype(np.float64)
+        d = self._C.shape[1]
+        ent, leaves = [], []
+
+        def visit(i):
+            kids = [c if c in pos else None for c in (2 * i, 2 * i + 1)]
+            if kids == [None, None]:
+                leaves.append(pos[i])
+                return -len(leaves)
+            e = len(ent)
+            ent.append(None)
+            tg = [None if c is None else visit(c) for c in kids]
+            h, t = _split_entry(*(None if c is None else Ct[pos[c]] for c in kids), d)
+            ent[e] = (h, t, tg[0] if tg[0] is not None else tg[1], tg[1] if tg[1] is not None else tg[0])
+            return e
+        if visit(1) < 0:             # the root is the only cluster
+            ent.append((np.zeros(d), np.inf, -1, -1))
+        return dict(h=np.array([e[0] for e in ent]), t=[e[1] for e in ent], left=[e[2] for e in ent],
+                    right=[e[3] for e in ent], leaves=np.array(leaves, dtype=np.int64))
+
+    def _descend(self, X, tab, w=None):
+        """(leaf, cost, bad) of the rows X by tree descent"""
+        if X.shape[0] == 0:
+            z = torch.zeros((), dtype=torch.float64, device=X.device)
+            return torch.zeros(0, dtype=torch.int32, device=X.device), z, z
+        return K.bisect_step(X, tab["h"], tab["t"], tab["left"], tab["right"], K.BISECT_PREDICT, None, w,
+                             self.getDistanceMeasure() == "cosine", self._shift, self._C[tab["leaves"]])
+
+    def clusterCenters(self):
+        return [c.copy() for c in self._C[self._tables()["leaves"]]]
+
+    @property
+    def hasSummary(self):
+        return self.summary is not None
+
+    def predict(self, features):
+        x = np.asarray(features.toArray() if hasattr(features, "toArray") else features, dtype=np.float64)
+        return int(self._descend(torch.from_numpy(x.reshape(1, -1).copy()), self._tables())[0][0])
+
+    def computeCost(self, dataset):
+        X, _, _ = local_xyw(dataset, self.getFeaturesCol(), keep_f64=True)
+        comm = dataset._session.comm
+        t = self._descend(X, self._tables())[1].reshape(1).to(comm.device)
+        comm.all_reduce(t)
+        return float(t)
+
+    def _transform(self, dataset):
+        fc, pc = self.getFeaturesCol(), self.getPredictionCol()
+        require_vector(dataset, fc)
+        tab = self._tables()
+
+        def fn(b, ctx):
+            X = b.columns[fc].values
+            X = X if X.dtype == torch.float64 else X.float()   # Double vectors: the fp64 host formulation
+            return b.with_column(pc, ColumnData(self._descend(X, tab)[0], T.IntegerType()))
+        return dataset._new(MapPlan(dataset._plan, "BisectingKMeansModel", fn))
+
+    def _save_state(self):
+        return {}, {"index": torch.tensor(self._index), "centers": torch.tensor(self._C),
+                    "costs": torch.tensor(self._cost), "weights": torch.tensor(self._W),
+                    "shift": torch.tensor(self._shift)}
+
+    def _load_state(self, extra, tensors, stages):
+        self._index = tensors["index"].numpy()
+        self._C = tensors["centers"].numpy()
+        self._cost = tensors["costs"].numpy()
+        self._W = tensors["weights"].numpy()
+        self._shift = tensors["shift"].numpy()
+        self.summary = None
 
 
 # ======================================================================================= GaussianMixture

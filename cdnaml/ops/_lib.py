@@ -255,6 +255,9 @@ _SIGS = {
     "cdna_cluster_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p], c_int),
     "cdna_cluster_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                            c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_bisect_plan": ([c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p], c_int),
+    "cdna_bisect_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "cdna_fm_step": ([c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_uint64, c_int64, c_double, c_uint32, c_void_p, c_void_p, c_void_p,
                       c_void_p], c_int),

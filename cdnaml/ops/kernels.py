@@ -3603,6 +3603,189 @@ def cluster_step(X: torch.Tensor, centres, mode: int = CLUSTER_STEP, w: Optional
     return (assign, sums, N, cost, bad) if step else (assign, cost, bad)
 
 
+# ------------------------------------------------------------ K33 bisect_step (bisect.hip)
+BISECT_STEP, BISECT_ASSIGN, BISECT_PREDICT = 0, 1, 2
+BISECT_MAX_D = 128             # the fused kernel's range: fp32 rows with d <= 128,
+BISECT_MAX_ENTRIES = 64        # at most 64 entries for STEP and ASSIGN,
+BISECT_MAX_LEAVES = 128        # at most 128 entries and 128 leaves for PREDICT
+BISECT_HOST_ELEMS = 1 << 22    # fp64 entries (rows x d) per pass of the host formulation
+
+
+def _bisect_native_plan(X: torch.Tensor, entries: int, leaves: int, mode: int):
+    if X.dim() != 2 or X.shape[0] == 0:
+        return None, X
+    return _row_plan(X, "cdna_bisect_plan", 12, X.shape[1], min(int(entries), 1 << 30), min(int(leaves), 1 << 30),
+                     int(mode))
+
+
+def bisect_plan(X: torch.Tensor, entries: int, mode: int = BISECT_STEP, leaves: int = 1) -> Dict[str, object]:
+    """What :func:`bisect_step` runs for these operands, from the dispatch's own host function (nothing is
+    launched): ``path`` "native" or "host"; for the native path ``mode``, ``slots`` (32 x 32 sum tiles per wave of a
+    STEP: 1, 2 or 4, else 0), ``vw`` (4: float4 row loads, 1: scalar loads), ``nblk``, ``rows_per_block``,
+    ``blocks_per_cu`` (of the one round of resident blocks), ``tiles``, ``lds`` (bytes per block: the head, the row
+    tile and the hyperplanes; the leaf centres of a PREDICT stay in global memory), ``centres`` ("global" for PREDICT)
+    and ``fold_rows`` (rows a block accumulates in fp32 between folds into its fp64 slab)."""
+    out, _ = _bisect_native_plan(X, entries, leaves, mode)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "mode": int(mode), "slots": int(out[1]), "vw": int(out[2]), "nblk": int(out[3]),
+            "rows_per_block": int(out[4]), "blocks_per_cu": int(out[10]), "tiles": int(out[5]), "lds": int(out[6]),
+            "centres": "global" if mode == BISECT_PREDICT else None, "fold_rows": int(out[9])}
+
+
+def bisect_step(X: torch.Tensor, h, t, left, right, mode: int = BISECT_STEP, node: Optional[torch.Tensor] = None,
+                w: Optional[torch.Tensor] = None, cosine: bool = False, shift=None, centres=None,
+                native: bool = True):
+    """One level step of bisecting k-means over the local rows, the commit of a level, or the descent of a tree.
+
+    X [n, d] fp32 or fp64.  The split table has M entries: hyperplanes ``h`` [M, d] (finite), thresholds ``t`` [M]
+    (+inf: every row goes left, -inf: right) and targets ``left`` / ``right`` [M]; a target >= 0 is another entry, a
+    target < 0 the leaf -1 - target.  A row at entry e takes the right side iff x~ . h_e > t_e (equality goes left),
+    with x~ = fl32(x - shift) (``shift`` [d], rounded to fp32; fp64 rows: x - shift) or, with ``cosine``, x~ = x in
+    the test and x^ = x / max(|x|, 1e-30) in the sums.  For fp32 rows h (and ``centres``) are rounded to fp32.  A row
+    whose |x~|^2 is NaN or >= CLUSTER_BAD_Q is *bad*: it goes left (PREDICT: to leaf 0), is counted and adds nothing
+    to the sums; the PREDICT cost becomes NaN or +inf.
+
+    BISECT_STEP: ``node`` [n] int32 is the entry every row stands at (-1: the row adds nothing).  Returns
+    ``(W [M, 2], cnt [M, 2], S [M, 2, d], Q [M, 2], bad)`` per entry and side: the sum of w, the row count, the sum of
+    w x~ (in the shifted frame) and the sum of w |x~|^2, fp64.  BISECT_ASSIGN: ``node`` is rewritten in place with the
+    target of every row's side; returns ``(node, bad)``.  BISECT_PREDICT: every row walks from entry 0 to a leaf (the
+    targets >= 0 of an entry must be greater than its index); ``centres`` [L, d] are the leaves' centres.  Returns
+    ``(leaf int32 [n], cost, bad)``, cost = sum of w D(x, c_leaf), D = sum (x~ - c~)^2 or 1 - cos.
+
+    fp32 X on a GPU with d <= BISECT_MAX_D and at most BISECT_MAX_ENTRIES entries (PREDICT: BISECT_MAX_LEAVES entries
+    and leaves) runs the K33 kernel: the side test a gathered fp64 dot product against hyperplanes in LDS, S on the
+    exact-fp32 MFMA (w rounded to fp32 there), W, cnt, Q and the cost in fp64, per-block partial sums reduced in a
+    fixed order (two calls on the same input return the same bits).  Everything else takes the host formulation: plain
+    fp64 torch ops in row chunks of BISECT_HOST_ELEMS / d rows (``native=False`` asks for it inside the range too).
+    """
+    if X.dim() != 2:
+        raise ValueError("bisect_step: X must be [n, d]")
+    if mode not in (BISECT_STEP, BISECT_ASSIGN, BISECT_PREDICT):
+        raise ValueError(f"bisect_step: mode {mode}")
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    n, d = X.shape
+    dev = X.device
+    f32 = X.dtype == torch.float32
+    H = np.asarray(h, dtype=np.float64).reshape(-1, d)
+    M = H.shape[0]
+    T_ = np.asarray(t, dtype=np.float64).reshape(-1)
+    tg = np.stack([np.asarray(left, dtype=np.int64).reshape(-1), np.asarray(right, dtype=np.int64).reshape(-1)])
+    if M < 1 or T_.shape[0] != M or tg.shape[1] != M or not np.isfinite(H).all() or np.isnan(T_).any():
+        raise ValueError(f"bisect_step: the table must be h [M >= 1, {d}] finite, t [M] and targets [M]")
+    if np.abs(tg).max() >= 1 << 31:
+        raise ValueError("bisect_step: a target is outside int32")
+    sh = np.zeros(d, dtype=np.float32)
+    if shift is not None and not cosine:
+        sh = torch.as_tensor(shift).detach().cpu().numpy().astype(np.float32).reshape(-1)
+        if sh.shape[0] != d or not np.isfinite(sh).all():
+            raise ValueError(f"bisect_step: shift must be finite [{d}]")
+    predict = mode == BISECT_PREDICT
+    L, C = 1, None
+    if predict:
+        C = np.asarray(centres, dtype=np.float64).reshape(-1, d)
+        L = C.shape[0]
+        if L < 1 or not np.isfinite(C).all():
+            raise ValueError(f"bisect_step: centres must be finite [L >= 1, {d}]")
+        C = C / np.maximum(np.linalg.norm(C, axis=1, keepdims=True), 1e-30) if cosine else C - sh.astype(np.float64)
+        idx = np.arange(M)[None, :]
+        if ((tg >= 0) & ((tg <= idx) | (tg >= M))).any() or (tg < -L).any():
+            raise ValueError("bisect_step: a PREDICT target must be a later entry or a leaf of centres")
+    else:
+        if node is None or node.dtype != torch.int32 or node.shape != (n,) or not node.is_contiguous() \
+                or node.device != dev:
+            raise ValueError("bisect_step: node must be a contiguous int32 [n] on the rows' device")
+    if f32:
+        with np.errstate(over="ignore"):
+            H = H.astype(np.float32)
+            C = None if C is None else C.astype(np.float32)
+        if not np.isfinite(H).all() or (C is not None and not np.isfinite(C).all()):
+            raise ValueError("bisect_step: the table overflows fp32")
+    wd = None if w is None else w.to(device=dev, dtype=torch.float64).contiguous()
+    plan, Xn = _bisect_native_plan(X, M, L, mode) if native else (None, X)
+    if plan is not None:
+        hyp = np.zeros((M, int(plan[7])), dtype=np.float32)
+        hyp[:, :d] = H
+        shp = np.zeros(BISECT_MAX_D, dtype=np.float32)
+        shp[:d] = sh
+        cen = np.zeros((L, int(plan[8])), dtype=np.float32)
+        if predict:
+            cen[:, :d] = C
+        hyp_d, thr_d, tg_d, sh_d, cen_d = upload(dev, hyp.reshape(-1), T_, tg.astype(np.int32).reshape(-1), shp,
+                                                 cen.reshape(-1))
+        if predict:
+            node = torch.empty(n, dtype=torch.int32, device=dev)
+        # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+        out = torch.empty(2 * M * (d + 3) + 2 if mode == BISECT_STEP else 2, dtype=torch.float64, device=dev)
+        ws = torch.empty(int(plan[11]), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().cdna_bisect_step(_ptr(Xn), n, Xn.stride(0), _ptr(wd), _ptr(hyp_d), _ptr(thr_d),
+                                               _ptr(tg_d), _ptr(sh_d), _ptr(cen_d), d, M, L, int(cosine), int(mode),
+                                               _ptr(node), _ptr(out), _ptr(ws), _stream(dev)), "cdna_bisect_step")
+        if mode == BISECT_ASSIGN:
+            return node, out[1]
+        if predict:
+            return node, out[0], out[1]
+        m2 = 2 * M
+        return (out[m2 * d:m2 * d + m2].view(M, 2), out[m2 * (d + 1):m2 * (d + 2)].view(M, 2),
+                out[:m2 * d].view(M, 2, d), out[m2 * (d + 2):m2 * (d + 3)].view(M, 2), out[m2 * (d + 3) + 1])
+    # host formulation, in row chunks
+    Hd = torch.from_numpy(H.astype(np.float64)).to(dev)
+    Td = torch.from_numpy(T_).to(dev)
+    Lt, Rt = (torch.from_numpy(v).to(dev) for v in tg)
+    Cd = None if C is None else torch.from_numpy(C.astype(np.float64)).to(dev)
+    sht = torch.from_numpy(sh).to(dev)
+    W = torch.zeros(2 * M, dtype=torch.float64, device=dev)
+    cnt, Q = torch.zeros_like(W), torch.zeros_like(W)
+    S = torch.zeros((2 * M, d), dtype=torch.float64, device=dev)
+    cost = torch.zeros((), dtype=torch.float64, device=dev)
+    bad = torch.zeros((), dtype=torch.float64, device=dev)
+    leaves = []
+    rows = max(1, BISECT_HOST_ELEMS // d)
+    for i0 in range(0, n, rows):
+        Xc = X[i0:i0 + rows]
+        xs = (Xc - sht).double() if f32 else Xc - sht.double()
+        q = (xs ** 2).sum(1)
+        isbad = ~(q < CLUSTER_BAD_Q)
+        inv = 1.0 / q.sqrt().clamp_min(1e-30)
+        wc = torch.ones_like(q) if wd is None else wd[i0:i0 + rows]
+        bad += isbad.sum()
+        if predict:
+            e = torch.zeros(xs.shape[0], dtype=torch.int64, device=dev)
+            for _ in range(M):
+                act = e >= 0
+                if not bool(act.any()):
+                    break
+                ee = e.clamp_min(0)
+                nx = torch.where((xs * Hd[ee]).sum(1) > Td[ee], Rt[ee], Lt[ee])
+                e = torch.where(act, nx, e)
+            leaf = torch.where(isbad | (e >= 0), torch.zeros_like(e), -1 - e)
+            c = 1.0 - (xs * Cd[leaf]).sum(1) * inv if cosine else ((xs - Cd[leaf]) ** 2).sum(1)
+            c = torch.where(isbad, torch.where(q.isnan(), q, torch.full_like(q, float("inf"))), c)
+            cost += (wc * c).sum()
+            leaves.append(leaf.int())
+            continue
+        e = node[i0:i0 + rows].long()
+        live = (e >= 0) & (e < M)
+        ee = torch.where(live, e, torch.zeros_like(e))
+        right_ = live & ~isbad & ((xs * Hd[ee]).sum(1) > Td[ee])
+        if mode == BISECT_ASSIGN:
+            node[i0:i0 + rows] = torch.where(live, torch.where(right_, Rt[ee], Lt[ee]), e).int()
+            continue
+        use = live & ~isbad
+        slot = (2 * ee + right_.long())[use]
+        xu, wu = (xs * inv[:, None] if cosine else xs)[use], wc[use]
+        W.index_add_(0, slot, wu)
+        cnt.index_add_(0, slot, torch.ones_like(wu))
+        Q.index_add_(0, slot, wu * (q * inv * inv if cosine else q)[use])
+        S.index_add_(0, slot, wu[:, None] * xu)
+    if mode == BISECT_ASSIGN:
+        return node, bad
+    if predict:
+        return (torch.cat(leaves) if leaves else torch.zeros(0, dtype=torch.int32, device=dev)), cost, bad
+    return W.view(M, 2), cnt.view(M, 2), S.view(M, 2, d), Q.view(M, 2), bad
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
