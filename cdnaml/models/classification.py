@@ -9,7 +9,9 @@ classifiers (DT / RF / GBT) share the histogram engine with class-count
 statistics (gini / entropy).  MultilayerPerceptronClassifier: every L-BFGS evaluation is one pass of the fused
 K24 kernel (forward, softmax cross-entropy, backward and weight gradients on the fp32 MFMA) plus one all-reduce of
 P + 1 doubles.  FMClassifier: Spark's minibatch gradient descent, every iteration one pass of the fused K25 kernel
-(shared with FMRegressor in :mod:`.regression`).  Reference: MLE 03 - Logistic Regression
+(shared with FMRegressor in :mod:`.regression`).  NaiveBayes (multinomial, complement, bernoulli, gaussian): the fit
+is one STATS pass of the fused K34 kernel (per-class fp64 moments on the fp64 MFMA) plus one all-reduce, transform one
+PREDICT pass of it.  Reference: MLE 03 - Logistic Regression
 Lab.py:99-158; Labs/ML 07L:42-209 (RandomForestClassifier + AUC).
 """
 from __future__ import annotations
@@ -33,7 +35,8 @@ from .regression import (_FM_PARAMS, _GBT, _PRED, _RF, _TREE, _FMModel, _TreeMod
                          tree_fit_prepare)
 from .tree.engine import ForestTrainer, TreeParams
 from .tree.forest import Forest
-from .util import VECTOR_F64_MAX, IllegalArgumentException, centered_gram, local_batch, local_xyw, require_vector
+from .util import (VECTOR_F64_MAX, IllegalArgumentException, centered_gram, lead_mean, local_batch, local_xyw,
+                   require_vector)
 
 # multinomial logistic regression: fp64 logits / gradients up to this many n*d*C multiply-adds per pass (course
 # sizes; Spark's Double), the fp32 device GEMMs above
@@ -825,10 +828,31 @@ class GBTClassificationModel(_TreeModelBase):
 
 
 # =============================================================== NaiveBayes
+# modelType: the value rule of the K34 STATS pass and what Spark says of a value that breaks it
+_NB_RULES = {
+    "multinomial": (K.NB_NONNEG, "requires nonnegative feature values"),
+    "complement": (K.NB_NONNEG, "requires nonnegative feature values"),
+    "bernoulli": (K.NB_BINARY, "requires 0 or 1 feature values"),
+    "gaussian": (K.NB_FINITE, ""),
+}
+
+
+def _nb_model_type(mt):
+    if mt not in _NB_RULES:
+        raise IllegalArgumentException(f"NaiveBayes: modelType '{mt}' is not one of {sorted(_NB_RULES)}")
+    return mt
+
+
 class NaiveBayes(Estimator):
+    """Spark's four naive Bayes models.  The fit is one pass of the K34 ``nb_step`` op over the local rows -- the
+    per-class fp64 sums W_c = sum w, S_c = sum w (x - s) and, for Gaussian, Q_c = sum w (x - s)^2 about a common
+    shift s near the mean -- plus one all-reduce of [S | Q | W | bad rows]; the parameters follow in fp64 numpy.
+    A row with a non-finite value, a negative value (multinomial, complement), a value other than 0 / 1
+    (bernoulli), a label that is not an integer in [0, numClasses) or a weight that is negative or not finite
+    raises.  Gaussian variances keep this project's floor: sigma = max(var, 1e-9) + 1e-9 max var."""
     _params = dict(_CLS, **{
         "smoothing": ("The smoothing parameter, should be >= 0", 1.0, TC.toFloat),
-        "modelType": ("multinomial, bernoulli or gaussian", "multinomial", TC.toString),
+        "modelType": ("multinomial, complement, bernoulli or gaussian", "multinomial", TC.toString),
         "weightCol": ("weight column name", None, TC.toString),
     })
 
@@ -837,32 +861,43 @@ class NaiveBayes(Estimator):
         keyword_init(self, kwargs)
 
     def _fit(self, dataset):
+        mt = _nb_model_type(self.getModelType())
+        rule, says = _NB_RULES[mt]
         X, y, w = local_xyw(dataset, self.getFeaturesCol(), self.getLabelCol(), self.getWeightCol())
         session = dataset._session
+        comm = session.comm
         C = max(_num_classes(session, y, None), 2)
         d = X.shape[1]
-        ww = w if w is not None else torch.ones_like(y)
-        Yoh = torch.nn.functional.one_hot(y.long(), C).double() * ww[:, None] if y.numel() else \
-            torch.zeros((0, C), dtype=torch.float64, device=X.device)
-        cnt = Yoh.sum(0)
-        S = (Yoh.float().T @ X).double()
-        SS = (Yoh.float().T @ (X * X)).double()
-        session.comm.all_reduce_many([cnt, S, SS])
-        lam = self.getSmoothing()
-        mt = self.getModelType()
-        pi = torch.log((cnt + lam) / (cnt.sum() + C * lam))
+        gauss = mt == "gaussian"
+        # every rank sums about the same point; a non-finite leading row must not spoil it (the row raises below)
+        shift = torch.nan_to_num(lead_mean(X, comm), nan=0.0, posinf=0.0, neginf=0.0).float() if gauss else None
+        S, Q, W, bad = K.nb_step(X, y, C, K.NB_STATS, w=w, quad=gauss, rule=rule, shift=shift)
+        comm.all_reduce_many([S, W, bad] + ([Q] if gauss else []))
+        nf, rb, lw = (int(v) for v in bad.cpu().numpy())
+        if nf or rb or lw:
+            what = [f"{nf} rows have a non-finite feature value"] if nf else []
+            what += [f"{rb} rows break the rule that modelType '{mt}' {says}"] if rb else []
+            what += [f"{lw} rows have an invalid label (not an integer in [0, {C})) or weight (negative or not "
+                     f"finite)"] if lw else []
+            raise IllegalArgumentException("NaiveBayes: " + "; ".join(what))
+        S, W = S.cpu().numpy(), W.cpu().numpy()
+        lam = float(self.getSmoothing())
+        pi = np.log(W + lam) - np.log(W.sum() + C * lam)
+        sigma = None
         if mt == "multinomial":
-            theta = torch.log((S + lam) / (S.sum(1, keepdim=True) + d * lam))
-            sigma = None
+            theta = np.log(S + lam) - np.log(S.sum(1, keepdims=True) + d * lam)
         elif mt == "bernoulli":
-            theta = torch.log((S + lam) / (cnt[:, None] + 2 * lam))
-            sigma = None
+            theta = np.log(S + lam) - np.log(W[:, None] + 2 * lam)
+        elif mt == "complement":
+            comp = S.sum(0, keepdims=True) - S + lam
+            theta = np.log(comp.sum(1, keepdims=True)) - np.log(comp)
         else:
-            mu = S / cnt.clamp_min(1)[:, None]
-            var = SS / cnt.clamp_min(1)[:, None] - mu * mu
-            theta, sigma = mu, var.clamp_min(1e-9) + 1e-9 * float(var.max())
-        return NaiveBayesModel(pi.cpu().numpy(), theta.cpu().numpy(), None if sigma is None else sigma.cpu().numpy(),
-                               mt)
+            Wd = np.maximum(W, 1.0)[:, None]
+            m1 = S / Wd
+            var = np.maximum(Q.cpu().numpy() / Wd - m1 * m1, 0.0)
+            theta = shift.double().cpu().numpy()[None, :] + m1
+            sigma = np.maximum(var, 1e-9) + 1e-9 * float(var.max())
+        return NaiveBayesModel(pi, theta, sigma, mt)
 
 
 class NaiveBayesModel(Model):
@@ -874,6 +909,7 @@ class NaiveBayesModel(Model):
         self._theta = np.asarray(theta if theta is not None else np.zeros((0, 0)))
         self._sigma = None if sigma is None else np.asarray(sigma)
         self._mt = modelType
+        self._nb_tables = None
 
     @property
     def pi(self):
@@ -883,27 +919,42 @@ class NaiveBayesModel(Model):
     def theta(self):
         return DenseMatrix(self._theta.shape[0], self._theta.shape[1], self._theta.T.reshape(-1))
 
+    @property
+    def sigma(self):
+        """The Gaussian model's variances [numClasses, numFeatures]; an empty matrix for the other model types."""
+        if self._sigma is None:
+            return DenseMatrix(0, 0, np.zeros(0))
+        return DenseMatrix(self._sigma.shape[0], self._sigma.shape[1], self._sigma.T.reshape(-1))
+
+    def _tables(self):
+        """The K34 PREDICT tables of this model (made once, their device copies once per device)."""
+        if self._nb_tables is None:
+            mt = _nb_model_type(self._mt)
+            pi, th = np.asarray(self._pi, dtype=np.float64), np.asarray(self._theta, dtype=np.float64)
+            if mt == "multinomial":
+                self._nb_tables = K.NbTables.linear(th, pi)
+            elif mt == "complement":
+                self._nb_tables = K.NbTables.linear(th, np.zeros_like(pi))
+            elif mt == "bernoulli":
+                neg = np.log1p(-np.minimum(np.exp(th), 1 - 1e-12))
+                self._nb_tables = K.NbTables.linear(th - neg, pi + neg.sum(1))
+            else:
+                # the shift of the quadratic form: the mean of the class means, as fp32
+                sg = np.asarray(self._sigma, dtype=np.float64)
+                self._nb_tables = K.NbTables.gaussian(pi, th, sg, th.mean(0).astype(np.float32))
+        return self._nb_tables
+
     def _transform(self, dataset):
         fc = self.getFeaturesCol()
         names = (self.getRawPredictionCol(), self.getPredictionCol(), self.getProbabilityCol())
-        pi, th = torch.tensor(self._pi), torch.tensor(self._theta)
-        sg = None if self._sigma is None else torch.tensor(self._sigma)
-        mt = self._mt
+        tables = self._tables()
+        C = tables.T1.shape[0]
 
         def fn(b, ctx):
-            X = b.columns[fc].values.double()
-            if mt == "multinomial":
-                raw = X @ th.to(X.device).T + pi.to(X.device)
-            elif mt == "bernoulli":
-                t = th.to(X.device)
-                neg = torch.log1p(-torch.exp(t).clamp(max=1 - 1e-12))
-                raw = X @ (t - neg).T + neg.sum(1) + pi.to(X.device)
-            else:
-                mu, var = th.to(X.device), sg.to(X.device)
-                raw = -0.5 * (((X[:, None, :] - mu[None]) ** 2) / var[None] + torch.log(2 * math.pi * var[None])).sum(
-                    2) + pi.to(X.device)
-            prob = torch.softmax(raw, 1)
-            return _append_cls_outputs(b, raw, prob, torch.argmax(prob, 1), names)
+            X = b.columns[fc].values
+            # one K34 PREDICT pass: the scores, the probabilities and the prediction
+            raw, prob, pred, _ = K.nb_step(X, None, C, K.NB_PREDICT, tables=tables)
+            return _append_cls_outputs(b, raw, prob, pred, names)
         return dataset._new(MapPlan(dataset._plan, "NaiveBayesModel", fn))
 
     def _save_state(self):
@@ -916,6 +967,7 @@ class NaiveBayesModel(Model):
         self._pi, self._theta = tensors["pi"].numpy(), tensors["theta"].numpy()
         self._sigma = tensors["sigma"].numpy() if "sigma" in tensors else None
         self._mt = extra["modelType"]
+        self._nb_tables = None
 
 
 class LinearSVC(Estimator):

@@ -3786,6 +3786,213 @@ def bisect_step(X: torch.Tensor, h, t, left, right, mode: int = BISECT_STEP, nod
     return W.view(M, 2), cnt.view(M, 2), S.view(M, 2, d), Q.view(M, 2), bad
 
 
+# ------------------------------------------------------------ K34 nb_step (nbayes.hip)
+NB_STATS, NB_PREDICT = 0, 1
+NB_FINITE, NB_NONNEG, NB_BINARY = 0, 1, 2   # the value rule of a STATS pass
+NB_MAX_D = 128                 # the fused kernel's range: fp32 rows with d <= 128
+NB_MAX_C = 32                  # and 2 <= C <= 32 classes
+NB_HOST_ELEMS = 1 << 24        # fp64 entries (rows x C x d, or rows x d) per pass of the host formulation
+
+
+def _nb_native_plan(X: torch.Tensor, C: int, mode: int, quad: bool):
+    return _row_plan(X, "cdna_nb_plan", 8, X.shape[-1], min(int(C), 1 << 30), int(mode), int(bool(quad)))
+
+
+def nb_plan(X: torch.Tensor, C: int, mode: int = NB_STATS, quad: bool = False) -> Dict[str, object]:
+    """What :func:`nb_step` runs for these operands, ``C`` classes, ``mode`` and ``quad`` (second moments, or the
+    Gaussian quadratic form), from the dispatch's own host function (nothing is launched): ``path`` "native" or
+    "host"; for the native path ``KB`` (16-class blocks of the fp64 MFMA), ``vw`` (4: float4 row loads, 1: scalar
+    loads), ``nblk``, ``rows_per_block``, ``lds`` (bytes per block), ``slot`` (workspace doubles per block, STATS)
+    and ``per_cu`` (resident blocks per CU)."""
+    out, _ = _nb_native_plan(X, C, mode, quad)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "KB": int(out[1]), "vw": int(out[2]), "nblk": int(out[3]),
+            "rows_per_block": int(out[4]), "lds": int(out[5]), "slot": int(out[6]), "per_cu": int(out[7])}
+
+
+def nb_on_range(X: torch.Tensor, C: int) -> bool:
+    """Whether rows like ``X``'s (its device, dtype and d) with ``C`` classes are on the K34 range, whatever their
+    number: the ranks of a distributed fit answer alike, also one whose shard is empty.  (Its :func:`nb_step` takes
+    the host formulation, which returns the same shapes, so every rank reduces the same buffer.)"""
+    return nb_plan(X if X.shape[0] else X.new_zeros((1, X.shape[1])), C)["path"] == "native"
+
+
+class NbTables:
+    """The parameters of a naive Bayes PREDICT pass, fp64 numpy, and their device copies (made once per device).
+    ``raw_c = g_c + sum_j T1[c][j] u_j (+ T2[c][j] u_j^2)``, u = x (quadratic: x - shift).  :meth:`linear` takes the
+    count models' table and constant; :meth:`gaussian` takes pi, mu and sigma and forms, with mu' = mu - shift,
+    T2 = -1 / (2 sigma), T1 = mu' / sigma and g = pi - sum_j (log(2 pi sigma) + mu'^2 / sigma) / 2."""
+
+    def __init__(self, T1, T2, g, shift=None, gauss=None):
+        self.T1, self.T2, self.g = T1, T2, g
+        self.shift = None if shift is None else np.asarray(shift, dtype=np.float32)
+        self.gauss = gauss          # (pi, mu, sigma): the host formulation's direct form
+        self._dev = {}
+
+    @classmethod
+    def linear(cls, theta, const):
+        return cls(np.asarray(theta, dtype=np.float64), None, np.asarray(const, dtype=np.float64).reshape(-1))
+
+    @classmethod
+    def gaussian(cls, pi, mu, sigma, shift):
+        pi, mu, sigma = (np.asarray(v, dtype=np.float64) for v in (pi, mu, sigma))
+        shift = np.asarray(shift, dtype=np.float32)
+        mp = mu - shift.astype(np.float64)
+        g = pi - 0.5 * (np.log(2.0 * math.pi * sigma) + mp * mp / sigma).sum(1)
+        return cls(mp / sigma, -0.5 / sigma, g, shift, (pi, mu, sigma))
+
+    @property
+    def quad(self) -> bool:
+        return self.T2 is not None
+
+    def on(self, dev, KB: int):
+        """(T1, T2, g, shift) on ``dev`` in the kernel's layout: [d rounded up to 4][16 KB], class c in column c."""
+        key = (str(dev), KB)
+        if key not in self._dev:
+            C, d = self.T1.shape
+
+            def tab(T):
+                t = np.zeros(((d + 3) // 4 * 4, 16 * KB), dtype=np.float64)
+                t[:d, :C] = T.T
+                return t.reshape(-1)
+            arrs = [tab(self.T1), self.g] + ([tab(self.T2), self.shift] if self.quad else [])
+            up = upload(dev, *arrs)
+            self._dev[key] = (up[0], up[2] if self.quad else None, up[1], up[3] if self.quad else None)
+        return self._dev[key]
+
+
+def nb_step(X: torch.Tensor, y: Optional[torch.Tensor], C: int, mode: int = NB_STATS,
+            w: Optional[torch.Tensor] = None, quad: bool = False, rule: int = NB_FINITE, shift=None,
+            tables: Optional[NbTables] = None, native: bool = True):
+    """The per-class weighted moments of the local rows, or a naive Bayes model's predictions for them.
+
+    X [n, d] fp32 or fp64, all arithmetic fp64.
+
+    NB_STATS: ``y`` [n] labels, ``w`` [n] row weights or None, ``shift`` [d] (used as fp32; None: zeros).  Returns
+    (S [C, d], Q [C, d] or None, W [C], bad [3]) fp64: W_c = sum w, S_c = sum w (x - shift), and with ``quad``
+    Q_c = sum w (x - shift)^2, over the rows of label c.  A row is bad when a value is non-finite, a value breaks
+    ``rule`` (NB_FINITE: none; NB_NONNEG: negative; NB_BINARY: not 0 or 1), the label is not an integer in [0, C), or
+    the weight is not finite or negative; ``bad`` counts such rows by the first of [non-finite value, rule-breaking
+    value, bad label or weight] that applies, and a bad row adds exactly nothing to the sums.  Integer-valued inputs
+    with integer weights give exact integer sums (below 2^53).
+
+    NB_PREDICT: ``tables`` an :class:`NbTables`.  Returns (raw [n, C], prob [n, C] fp64, pred [n] int32, bad):
+    prob = softmax(raw), pred the lowest index among the largest probabilities; a row with a non-finite feature gets
+    NaN raw and prob and pred 0 and is counted in ``bad``.
+
+    fp32 X on a GPU with d <= NB_MAX_D and 2 <= C <= NB_MAX_C (any n >= 1, row stride and alignment) runs the K34
+    kernel: one pass, the products on the fp64 MFMA, per-block partial sums reduced in a fixed order (two calls on
+    the same input return the same bits).  Everything else takes the host formulation: plain fp64 torch ops, at most
+    NB_HOST_ELEMS intermediate entries at a time (``native=False`` asks for it inside the range too); its Gaussian
+    predict is the direct form sum (x - mu)^2 / sigma.
+    """
+    if X.dim() != 2:
+        raise ValueError("nb_step: X must be [n, d]")
+    if mode not in (NB_STATS, NB_PREDICT) or rule not in (NB_FINITE, NB_NONNEG, NB_BINARY):
+        raise ValueError(f"nb_step: mode {mode}, rule {rule}")
+    n, d = X.shape
+    C = int(C)
+    dev = X.device
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.float()
+    if mode == NB_STATS:
+        y = y.to(device=dev, dtype=torch.float64).contiguous()
+        w = None if w is None else w.to(device=dev, dtype=torch.float64).contiguous()
+        if y.shape != (n,) or (w is not None and w.shape != (n,)):
+            raise ValueError("nb_step: y and w must be [n]")
+        sh = np.zeros(d, dtype=np.float32) if shift is None else np.asarray(
+            shift.detach().cpu().numpy() if isinstance(shift, torch.Tensor) else shift, dtype=np.float32).reshape(-1)
+        if sh.shape[0] != d:
+            raise ValueError(f"nb_step: shift of {sh.shape[0]} for d = {d}")
+    else:
+        quad = tables.quad
+        if tables.T1.shape != (C, d):
+            raise ValueError(f"nb_step: tables {tables.T1.shape} for C = {C}, d = {d}")
+    plan, Xn = _nb_native_plan(X, C, mode, quad) if native else (None, X)
+    if plan is not None:
+        L = _lib.lib()
+        if mode == NB_STATS:
+            sh_d = None if shift is None else upload(dev, sh)[0]
+            # every entry of out is written by the reduction, every workspace entry it reads by the step kernel
+            slot = int(plan[6])
+            out = torch.empty(slot, dtype=torch.float64, device=dev)
+            ws = torch.empty(int(plan[3]) * slot, dtype=torch.float64, device=dev)
+            _lib.check(L.cdna_nb_step(_ptr(Xn), n, Xn.stride(0), _ptr(y), _ptr(w), _ptr(sh_d), None, None, None, d, C,
+                                      int(rule), int(quad), NB_STATS, _ptr(out), _ptr(ws), None, None, None, None,
+                                      _stream(dev)), "cdna_nb_step")
+            G = C * d
+            q0 = G * (2 if quad else 1)
+            return (out[:G].view(C, d), out[G:2 * G].view(C, d) if quad else None, out[q0:q0 + C],
+                    out[q0 + C:q0 + C + 3])
+        T1_d, T2_d, g_d, sh_d = tables.on(dev, int(plan[1]))
+        raw = torch.empty((n, C), dtype=torch.float64, device=dev)
+        prob = torch.empty((n, C), dtype=torch.float64, device=dev)
+        pred = torch.empty(n, dtype=torch.int32, device=dev)
+        nbad = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(L.cdna_nb_step(_ptr(Xn), n, Xn.stride(0), None, None, _ptr(sh_d), _ptr(T1_d), _ptr(T2_d),
+                                  _ptr(g_d), d, C, NB_FINITE, int(quad), NB_PREDICT, None, None, _ptr(raw),
+                                  _ptr(prob), _ptr(pred), _ptr(nbad), _stream(dev)), "cdna_nb_step")
+        return raw, prob, pred, nbad[0].double()
+    # host formulation in row chunks
+    if mode == NB_STATS:
+        rows = max(1, NB_HOST_ELEMS // max(d, 1))
+        sh_t = torch.from_numpy(sh).to(dev).double()
+        S = torch.zeros((C, d), dtype=torch.float64, device=dev)
+        Q = torch.zeros((C, d), dtype=torch.float64, device=dev) if quad else None
+        W = torch.zeros(C, dtype=torch.float64, device=dev)
+        bad = torch.zeros(3, dtype=torch.float64, device=dev)
+        for i0 in range(0, n, rows):
+            Xc = X[i0:i0 + rows].double()
+            yc = y[i0:i0 + rows]
+            wc = torch.ones_like(yc) if w is None else w[i0:i0 + rows]
+            nf = ~torch.isfinite(Xc).all(1)
+            if rule == NB_NONNEG:
+                rb = (Xc < 0).any(1)
+            elif rule == NB_BINARY:
+                rb = ((Xc != 0) & (Xc != 1)).any(1)
+            else:
+                rb = torch.zeros_like(nf)
+            lw = ~((yc >= 0) & (yc < C) & (yc == yc.floor()) & torch.isfinite(wc) & (wc >= 0))
+            ok = ~(nf | rb | lw)
+            bad += torch.stack([nf.sum(), (rb & ~nf).sum(), (lw & ~nf & ~rb).sum()]).double()
+            zero = torch.zeros_like(wc)
+            R = torch.nn.functional.one_hot(torch.where(ok, yc, zero).long(), C).double() * \
+                torch.where(ok, wc, zero)[:, None]
+            U = torch.where(ok[:, None], Xc - sh_t, zero[:, None])      # predicated: never a NaN times zero
+            S += R.T @ U
+            if quad:
+                Q += R.T @ (U * U)
+            W += R.sum(0)
+        return S, Q, W, bad
+    rows = max(1, NB_HOST_ELEMS // max(d * (C if quad else 1), 1))
+    g_t = torch.from_numpy(tables.g).to(dev)
+    if quad:
+        pi_t, mu_t, sg_t = (torch.from_numpy(v).to(dev) for v in tables.gauss)
+        const = pi_t - 0.5 * torch.log(2.0 * math.pi * sg_t).sum(1)
+    else:
+        T1_t = torch.from_numpy(tables.T1).to(dev)
+    outs = []
+    nbad = torch.zeros((), dtype=torch.float64, device=dev)
+    for i0 in range(0, n, rows):
+        Xc = X[i0:i0 + rows].double()
+        if quad:
+            raw = const - 0.5 * ((Xc[:, None, :] - mu_t[None]) ** 2 / sg_t[None]).sum(2)
+        else:
+            raw = Xc @ T1_t.T + g_t
+        prob = torch.softmax(raw, 1)
+        pred = _first_argmax(prob)
+        nf = ~torch.isfinite(Xc).all(1)
+        nan = torch.full_like(raw, math.nan)
+        outs.append((torch.where(nf[:, None], nan, raw), torch.where(nf[:, None], nan, prob),
+                     torch.where(nf, torch.zeros_like(pred), pred)))
+        nbad += nf.sum()
+    if not outs:
+        z0 = torch.zeros((0, C), dtype=torch.float64, device=dev)
+        return z0, z0.clone(), torch.zeros(0, dtype=torch.int32, device=dev), nbad
+    return tuple(torch.cat(p) for p in zip(*outs)) + (nbad,)
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
