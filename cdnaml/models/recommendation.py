@@ -361,13 +361,13 @@ class ALSModel(Model):
         import pandas as pd
         from ..session import SparkSession
         s = SparkSession.getActiveSession()
-        dev = s.device
-        St, Dt = torch.from_numpy(S).to(dev), torch.from_numpy(D).to(dev)
-        scores = St @ Dt.T
-        kk = min(k, Dt.shape[0])
-        top = torch.topk(scores, kk, dim=1)
-        idx, val = top.indices.cpu().numpy(), top.values.cpu().numpy()
-        recs = [[{dst_name: int(dst_ids[j]), "rating": float(v)} for j, v in zip(ri, rv)] for ri, rv in zip(idx, val)]
+        # the two factor tables go up once, ns x k values and positions come back (K35: no ns x nd score matrix)
+        from ..ops import kernels as K
+        St, Dt = (torch.from_numpy(np.ascontiguousarray(F, dtype=np.float32)).to(s.device) for F in (S, D))
+        val, idx = K.als_topk(St, Dt, int(k))
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        recs = [[{dst_name: int(dst_ids[j]), "rating": float(v)} for j, v in zip(ri, rv) if j >= 0]
+                for ri, rv in zip(idx, val)]
         pdf = pd.DataFrame({src_name: src_ids.astype(np.int32), "recommendations": [str(r) for r in recs]})
         df = s.createDataFrame(pdf)
         df._recs = recs
@@ -387,6 +387,13 @@ class ALSModel(Model):
         ok = (pos < len(self._uid)) & (self._uid[np.minimum(pos, len(self._uid) - 1)] == ids)
         return self._recommend(ids[ok], self._U[pos[ok]], self._iid, self._V, numItems, self.getUserCol(),
                                self.getItemCol())
+
+    def recommendForItemSubset(self, dataset, numUsers):
+        ids = np.array([r[0] for r in dataset.select(self.getItemCol()).distinct().collect()], dtype=np.int64)
+        pos = np.searchsorted(self._iid, ids)
+        ok = (pos < len(self._iid)) & (self._iid[np.minimum(pos, len(self._iid) - 1)] == ids)
+        return self._recommend(ids[ok], self._V[pos[ok]], self._uid, self._U, numUsers, self.getItemCol(),
+                               self.getUserCol())
 
     def _save_state(self):
         return {}, {"uid": torch.from_numpy(self._uid), "U": torch.from_numpy(self._U),

@@ -289,6 +289,9 @@ _SIGS = {
     "cdna_col_distinct": ([c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p], c_int),
     "cdna_col_recode": ([c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                          c_int64, c_void_p, c_void_p, c_void_p], c_int),
+    "cdna_als_topk_plan": ([c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p], c_int),
+    "cdna_als_topk": ([c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
+                       c_void_p, c_void_p], c_int),
 }
 
 

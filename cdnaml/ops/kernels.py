@@ -3993,6 +3993,99 @@ def nb_step(X: torch.Tensor, y: Optional[torch.Tensor], C: int, mode: int = NB_S
     return tuple(torch.cat(p) for p in zip(*outs)) + (nbad,)
 
 
+# ------------------------------------------------------------ K35 als_topk (topk.hip)
+TOPK_MAX_R = 128               # the fused kernel's range: fp32 factor rows of rank r <= 128
+TOPK_MAX_K = 64                # and k <= 64 recommendations a row
+TOPK_HOST_ELEMS = 1 << 24      # fp64 scores (source rows x destinations) per pass of the host formulation
+
+
+def _unit_rows(X: torch.Tensor) -> torch.Tensor:
+    return X if X.stride(1) == 1 and X.stride(0) >= X.shape[1] else X.contiguous()
+
+
+def _topk_native_plan(S: torch.Tensor, D: torch.Tensor, k: int):
+    if S.dim() != 2 or D.dim() != 2 or S.shape[1] != D.shape[1]:
+        raise ValueError(f"als_topk: S {tuple(S.shape)} and D {tuple(D.shape)} must be [ns, r] and [nd, r]")
+    if not (_native(S) and S.dtype == torch.float32 and D.dtype == torch.float32 and D.device == S.device):
+        return None, S, D
+    if not S.shape[0] or not D.shape[0]:
+        return None, S, D
+    S, D = _unit_rows(S), _unit_rows(D)
+    out = np.zeros(9, dtype=np.int64)
+    _lib.check(_lib.lib().cdna_als_topk_plan(_ptr(S), S.shape[0], S.stride(0), _ptr(D), D.shape[0], D.stride(0),
+                                             S.shape[1], min(int(k), 1 << 30), out.ctypes.data),
+               "cdna_als_topk_plan")
+    return (out if out[0] else None), S, D
+
+
+def als_topk_plan(S: torch.Tensor, D: torch.Tensor, k: int) -> Dict[str, object]:
+    """What :func:`als_topk` runs for these operands and ``k``, from the dispatch's own host function (nothing is
+    launched): ``path`` "native" or "host"; for the native path ``vw`` (4: float4 loads of D's rows, 1: scalar
+    loads), ``src_blocks`` (blocks of 128 source rows), ``slabs`` (destination slabs; more than one: the merge kernel
+    runs), ``rows_per_slab``, ``lds`` (bytes per block), ``workspace`` (bytes), ``per_cu`` (resident blocks per CU)
+    and ``cols`` (the columns the instantiation holds)."""
+    out, _, _ = _topk_native_plan(S, D, k)
+    if out is None:
+        return {"path": "host"}
+    return {"path": "native", "vw": int(out[1]), "src_blocks": int(out[2]), "slabs": int(out[3]),
+            "rows_per_slab": int(out[4]), "lds": int(out[5]), "workspace": int(out[6]), "per_cu": int(out[7]),
+            "cols": int(out[8])}
+
+
+def als_topk(S: torch.Tensor, D: torch.Tensor, k: int, native: bool = True):
+    """For every row of ``S`` [ns, r] the ``k`` rows of ``D`` [nd, r] with the largest dot product.
+
+    Returns (val [ns, k] fp32, idx [ns, k] int32) on S's device, each row in the order (score descending, position
+    ascending): among equal scores the lower position comes first, so the result is a function of the operands
+    alone.  A NaN score is never returned; when fewer than ``k`` destinations qualify the tail of the row is
+    ``idx = -1``, ``val = -inf``.
+
+    fp32 factors on a GPU with r <= TOPK_MAX_R and k <= TOPK_MAX_K run the K35 kernel: the scores on the fp32 MFMA,
+    the selection fused behind them, nothing of size ns x nd is ever stored.  Everything else takes the host
+    formulation (``native=False`` asks for it inside the range too): fp64 scores from the given factors, at most
+    TOPK_HOST_ELEMS of them at a time, and a stable sort.
+    """
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"als_topk: k = {k}")
+    plan, Sn, Dn = _topk_native_plan(S, D, k) if native else (None, S, D)
+    dev = S.device
+    ns, nd = S.shape[0], D.shape[0]
+    if plan is not None:
+        val = torch.empty((ns, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((ns, k), dtype=torch.int32, device=dev)
+        # every workspace entry the merge reads is written by the first kernel
+        ws = torch.empty(int(plan[6]) // 8, dtype=torch.float64, device=dev) if plan[6] else None
+        _lib.check(_lib.lib().cdna_als_topk(_ptr(Sn), ns, Sn.stride(0), _ptr(Dn), nd, Dn.stride(0), Sn.shape[1], k,
+                                            _ptr(val), _ptr(idx), _ptr(ws), _stream(dev)), "cdna_als_topk")
+        return val, idx
+    # host formulation in chunks of source rows
+    val = torch.full((ns, k), -math.inf, dtype=torch.float32, device=dev)
+    idx = torch.full((ns, k), -1, dtype=torch.int32, device=dev)
+    kk = min(k, nd)
+    if not ns or not kk:
+        return val, idx
+    Dd = D.to(dev).double()
+    rows = max(1, TOPK_HOST_ELEMS // nd)
+    slot = torch.arange(kk, device=dev)
+    for i0 in range(0, ns, rows):
+        sc = S[i0:i0 + rows].double() @ Dd.T
+        nan = torch.isnan(sc)
+        key = sc.masked_fill(nan, -math.inf)
+        if bool(nan.any()):
+            # NaN scores behind every real one, scores of -inf included: a stable pre-sort on the NaN flag
+            first = torch.sort(nan.to(torch.uint8), dim=1, stable=True).indices
+            srt = torch.sort(key.gather(1, first), dim=1, descending=True, stable=True)
+            pos = first.gather(1, srt.indices[:, :kk])
+        else:
+            srt = torch.sort(key, dim=1, descending=True, stable=True)
+            pos = srt.indices[:, :kk]
+        ok = slot[None, :] < (~nan).sum(1, keepdim=True)
+        val[i0:i0 + rows, :kk] = torch.where(ok, srt.values[:, :kk], torch.full_like(srt.values[:, :kk], -math.inf))
+        idx[i0:i0 + rows, :kk] = torch.where(ok, pos, torch.full_like(pos, -1))
+    return val, idx
+
+
 # ------------------------------------------------------------ segment mode (seg.hip)
 SEG_HIST_CHUNK = 262144
 # lane10 record chunks (levels 2-4 of the headline): at most this many records per block.  The records of a slot
